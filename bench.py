@@ -2,23 +2,35 @@
 """Headline benchmark: ray-surface-intersections/s of Raytracer.trace() on the double-Gauss scene.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--no-pol] [--backend nccl|gloo]
+                    [--dump-outputs DIR] [--full [--skip-cpu] [--skip-configs] [--cpu-seconds S]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one call of `Raytracer.trace(N)` -- the call the reference times in tests/benchmark.py:81-86 -- on one
 bundle of synthetic rays: on-device ray generation from the five point sources, all 15 tracing surfaces, all
 section stores, the event counters back on the host.  Workload = BASELINE.json configs[1]: double_gauss.py
-geometry, 10 M rays per GPU, 3 wavelengths (FDC lines), polarisation on.  Every step draws a fresh seed.
+geometry, 10 M rays per GPU, 3 wavelengths (FDC lines), polarisation on.  Every step draws a fresh seed from NumPy's
+generator, which is seeded once more right before the warm-up steps: with the same arguments every run traces the
+same rays.
 
 `--gpus N` without a torch.distributed environment starts the N ranks itself (a child `torch.distributed.run`,
 before this process makes any GPU call); launched by torch.distributed.run it is one of the ranks.  Rays are
-sharded, every rank traces its own bundle (weak scaling), no data-path collective inside the step; after the
-timed region the detector histograms are all-reduced once (RCCL) to exercise the exchange step.  With fewer
+sharded, every rank traces its own bundle (weak scaling), no data-path collective inside the step.  With fewer
 devices than ranks the ranks share devices and the collectives run over gloo on host copies (a rehearsal of the
 multi-rank code path, labelled as such in the output).
 
-Rank 0 prints ONE JSON line (contract in the task description) carrying `roofline` (dominant kernel: algorithmic
-bytes / HIP-event kernel time against the 8 TB/s HBM peak, plus the f64 issue fraction) and `cpu_baseline` (the
-CPU oracle, a scalar port of the reference, timed on a bounded sample on the host cores).
+A plain run sets up, settles the clocks, runs the W warm-up and the K timed steps and prints ONE JSON line (rank 0)
+with the headline and `roofline` (dominant kernel: algorithmic bytes / HIP-event kernel time of the timed steps
+against the 8 TB/s HBM peak, plus the f64 issue fraction from committed counter profiles).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0) as DIR/<name>.npy: the event
+counters whole and the ray storage (positions, directions, polarisations, weights, refraction indices, wavelengths) of
+a fixed, seeded sample of rays, about 35 MB.  Entries that are NaN or inf there (direction and polarisation after a
+total internal reflection) are written as 0 and located by <name>_nonfinite.
+
+`--full` adds everything that takes runs of its own, after the timed region: back-to-back raw launches, the detector
+image and the one exchange step (histogram all-reduce, RCCL), the no_pol setting, `cpu_baseline` (the CPU oracle, a
+scalar port of the reference, timed on a bounded sample on the host cores; `--skip-cpu`), the other BASELINE
+configurations and the sharded renders of configs 4 and 5 (`--skip-configs`).
 """
 from __future__ import annotations
 
@@ -49,13 +61,22 @@ def parse():
     ap.add_argument("--warmup", type=int, default=30)  # the first ~10 launches run while the clocks settle
     ap.add_argument("--rays", type=int, default=10_000_000, help="rays per GPU and step")
     ap.add_argument("--no-pol", action="store_true")
-    ap.add_argument("--skip-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the raw launches, the detector image and exchange step, "
+                         "the no_pol setting, the CPU baseline and the other BASELINE configurations")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--skip-configs", action="store_true", help="skip the `configs` block (the other BASELINE configs "
-                                                                "and config 4's sharded render, after the timed region)")
+    ap.add_argument("--skip-configs", action="store_true", help="with --full: skip the `configs` block (the other "
+                                                                "BASELINE configs and the sharded renders of configs "
+                                                                "4 and 5, after the timed region)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo: collectives on "
                                                       "host copies, also picked when ranks have to share a device)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -77,6 +98,8 @@ def spawn_ranks(args) -> int:
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--rays", str(args.rays), "--backend", backend, "--cpu-seconds", str(args.cpu_seconds)]
     cmd += ["--no-pol"] if args.no_pol else []
+    cmd += ["--full"] if args.full else []
+    cmd += ["--dump-outputs", str(pathlib.Path(args.dump_outputs).resolve())] if args.dump_outputs else []
     cmd += ["--skip-cpu"] if args.skip_cpu else []
     cmd += ["--skip-configs"] if args.skip_configs else []
     env = dict(os.environ)
@@ -382,6 +405,46 @@ def committed_profile(name: str, pol: bool, N: int):
     return best
 
 
+DUMP_SAMPLE_RAYS = 32768  # rays of the storage written by --dump-outputs (~850 B each with polarisation)
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(RT, out_dir: str) -> None:
+    """What the last `Raytracer.trace(N)` gave its caller, as float32 / float64 .npy files of finite numbers: the event
+    counters (`RT._msgs`) whole and the ray storage of a fixed, seeded, sorted sample of ray indices, gathered on the
+    device (the whole storage is 8.4 GB at 10 M rays)."""
+    import numpy as np
+    import torch
+    out = pathlib.Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    r = RT.rays
+    n = min(DUMP_SAMPLE_RAYS, r.N)
+    ind = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(r.N, size=n, replace=False))
+    idx = torch.from_numpy(ind.astype(np.int64)).to(r._dev["s"].device)
+    sections = slice(None)
+    arrays = {
+        "msgs": np.asarray(RT._msgs, dtype=np.float64),  # (event kind, section) counts, exact in float64
+        "ray_index": ind.astype(np.float64),
+        "p": r._select("p", ind, sections),              # (n, sections, 3) float64
+        "s0": r._dev["s"].view(3, r._Np)[:, idx].t().cpu().numpy(),  # (n, 3) float64, every ray's last direction
+        "w": r._select("w", ind, sections),              # (n, sections) float32
+        "n": r._select("n", ind, sections),              # (n, sections) float64
+        "wl": r._select("wl", ind, None),                # (n,) float32
+    }
+    if not r.no_pol:
+        arrays["pol"] = r._select("pol", ind, sections)  # (n, sections, 3) float32
+    # Entries the caller receives as NaN or inf -- after a total internal reflection the reference's direction s' and the
+    # polarisation built from it are NaN (raytracer.py:801-807, 861-872; the ray's weight is 0 from there on) -- are
+    # written as 0 and located by <name>_nonfinite (0 finite, 1 NaN, 2 +inf, 3 -inf): every file holds plain numbers.
+    for name, a in list(arrays.items()):
+        bad = ~np.isfinite(a)
+        if bad.any():
+            arrays[name + "_nonfinite"] = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1, 2, 3], 0).astype(np.float32)
+            arrays[name] = np.where(bad, 0, a).astype(a.dtype)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -472,6 +535,9 @@ def main():
             if settled:
                 break
 
+    # The settle phase takes a varying number of traces: the warm-up and timed steps draw their seeds anew, so that
+    # every run with the same arguments traces the same rays (--dump-outputs).
+    np.random.seed(1000 + rank)
     with ot.global_options.no_warnings():
         for i in range(args.warmup):
             RT.trace(N)
@@ -495,46 +561,48 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     t_max = float(t.item())
 
-    # ---- after the timed region: raw launches, detector image + the one exchange step (histogram all-reduce) ----
-    raw_ms = raw_launches(RT, lib, N, args.steps)
-    with ot.global_options.no_warnings():
-        RT.trace(N)  # (the raw launches bypassed the tracer's bookkeeping)
-        det_extent = [-45., 45., -45., 45.]
-        RT.detector_image(extent=det_extent, _keep_on_device=True)  # first call pays one-off table upload / lazy init
-        torch.cuda.synchronize()
-        td0 = time.perf_counter()
-        img = RT.detector_image(extent=det_extent, _keep_on_device=True)
-        torch.cuda.synchronize()
-    t_det = time.perf_counter() - td0
-    hist = img._dev
-    t_red = 0.0
-    if use_dist:
-        torch.cuda.synchronize()
-        tr0 = time.perf_counter()
-        D.allreduce_images([hist])  # the one exchange step: all-reduce of the (Ny, Nx, 4) f64 histogram (its lit window)
-        torch.cuda.synchronize()
-        t_red = time.perf_counter() - tr0
-        cnt = D.allreduce_counters(RT._msgs, device=None if on_host else dev)
-        assert cnt.sum() >= RT._msgs.sum()
-    total_power = float(hist[..., 3].sum().item())
+    if args.dump_outputs and rank == 0:  # before anything else traces into the storage
+        dump_outputs(RT, args.dump_outputs)
 
-    other = None
-    if world == 1 and not args.no_pol:  # same scene without polarisation tracking, outside the timed region
-        other = secondary_no_pol(ot, scenes, lib, N, args.steps)
+    # ---- --full, after the timed region: raw launches, detector image + the one exchange step (histogram all-reduce) ----
+    raw_ms = other = cpu = cfgs = sharded = sharded5 = None
+    if args.full:
+        raw_ms = raw_launches(RT, lib, N, args.steps)
+        with ot.global_options.no_warnings():
+            RT.trace(N)  # (the raw launches bypassed the tracer's bookkeeping)
+            det_extent = [-45., 45., -45., 45.]
+            RT.detector_image(extent=det_extent, _keep_on_device=True)  # first call pays one-off table upload / lazy init
+            torch.cuda.synchronize()
+            td0 = time.perf_counter()
+            img = RT.detector_image(extent=det_extent, _keep_on_device=True)
+            torch.cuda.synchronize()
+        t_det = time.perf_counter() - td0
+        hist = img._dev
+        t_red = 0.0
+        if use_dist:
+            torch.cuda.synchronize()
+            tr0 = time.perf_counter()
+            D.allreduce_images([hist])  # the one exchange step: all-reduce of the (Ny, Nx, 4) f64 histogram (its lit window)
+            torch.cuda.synchronize()
+            t_red = time.perf_counter() - tr0
+            cnt = D.allreduce_counters(RT._msgs, device=None if on_host else dev)
+            assert cnt.sum() >= RT._msgs.sum()
+        total_power = float(hist[..., 3].sum().item())
 
-    # ---- the other BASELINE configurations, after the timed region and with the headline's storage released ----
-    cpu = None
-    if rank == 0 and not args.skip_cpu and world == 1:  # CPU leg on rank 0 at N = 1 only (reads the first sections of the
-        cpu = cpu_baseline(RT, scene, args.cpu_seconds)  # headline's storage: before that is released)
-    cfgs = sharded = sharded5 = None
-    if not args.skip_configs:
-        del img, hist
-        RT.rays.__init__()
-        _release(torch, lib)
-        if world == 1:
-            cfgs = configs_block(ot, torch, lib, scenes)
-        sharded = c4_sharded_block(ot, torch, lib, scenes, dist if use_dist else None, use_dist, backend, dev, world)
-        sharded5 = c5_sharded_block(ot, torch, lib, scenes, dist if use_dist else None, use_dist, backend, dev, world)
+        if world == 1 and not args.no_pol:  # same scene without polarisation tracking, outside the timed region
+            other = secondary_no_pol(ot, scenes, lib, N, args.steps)
+
+        # ---- the other BASELINE configurations, after the timed region and with the headline's storage released ----
+        if rank == 0 and not args.skip_cpu and world == 1:  # CPU leg on rank 0 at N = 1 only (reads the first sections of the
+            cpu = cpu_baseline(RT, scene, args.cpu_seconds)  # headline's storage: before that is released)
+        if not args.skip_configs:
+            del img, hist
+            RT.rays.__init__()
+            _release(torch, lib)
+            if world == 1:
+                cfgs = configs_block(ot, torch, lib, scenes)
+            sharded = c4_sharded_block(ot, torch, lib, scenes, dist if use_dist else None, use_dist, backend, dev, world)
+            sharded5 = c5_sharded_block(ot, torch, lib, scenes, dist if use_dist else None, use_dist, backend, dev, world)
 
     if rank == 0:
         pol = not args.no_pol
@@ -584,11 +652,12 @@ def main():
                        "ranks_per_device": -(-world // ndev)},
             "roofline": roof,
             "api_overhead_ms": 1e3 * t_local / args.steps - kernel_ms,
-            "raw_kernel": {"ms_per_launch": raw_ms, "value": N * M / (raw_ms * 1e-3),
-                           "what": "back-to-back asynchronous ot_generate_and_trace launches, no host work between"},
-            "detector": {"rays_per_s": N / t_det, "ms": 1e3 * t_det, "allreduce_ms": 1e3 * t_red,
-                         "image_power_all_ranks": total_power},
         }
+        if raw_ms is not None:
+            out["raw_kernel"] = {"ms_per_launch": raw_ms, "value": N * M / (raw_ms * 1e-3),
+                                 "what": "back-to-back asynchronous ot_generate_and_trace launches, no host work between"}
+            out["detector"] = {"rays_per_s": N / t_det, "ms": 1e3 * t_det, "allreduce_ms": 1e3 * t_red,
+                               "image_power_all_ranks": total_power}
         if cfgs is not None:
             out["configs"] = cfgs
         if sharded is not None:

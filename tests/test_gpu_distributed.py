@@ -241,7 +241,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     one device here, so the collectives fall back to gloo) and rank 0 reports n_gpus = 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--rays", "1000000", "--skip-cpu"], env=env, capture_output=True, text=True, timeout=800)
+                        "--rays", "1000000", "--full", "--skip-cpu"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line, from rank 0"
@@ -265,8 +265,8 @@ def test_bench_line_carries_every_baseline_config():
     """One GPU: the driver's line has the `configs` block (C1 at 1e7 rays, C3, C4, C5, A1 at full size: trace kernel time and
     roofline fraction, detector image with an automatic and a given extent, the chunked render) and both sharded blocks."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "2", "--skip-cpu"], env=env,
-                       capture_output=True, text=True, timeout=800)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "2", "--full", "--skip-cpu"],
+                       env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -21,7 +21,7 @@ res = {n: [] for n, _ in arms}
 for r in range(rounds):
     for name, path in arms:
         env = dict(os.environ, OPTRACE_AMD_LIB=str((ROOT / path).resolve()))
-        out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--skip-cpu", "--steps", "40", "--warmup", "30"] + extra,
+        out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--skip-cpu", "--steps", "40", "--warmup", "30"] + extra,
                              env=env, capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

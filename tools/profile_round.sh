@@ -7,10 +7,10 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/profile
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$R/bench.py" --skip-cpu --skip-configs > "$OUT/bench_stats.log" 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -- python3 "$R/bench.py" --steps 3 --warmup 1 --skip-cpu --skip-configs > "$OUT/bench_fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write" -- python3 "$R/bench.py" --steps 3 --warmup 1 --skip-cpu --skip-configs > "$OUT/bench_write.log" 2>&1
-rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d "$OUT/sq" -- python3 "$R/bench.py" --steps 3 --warmup 1 --skip-cpu --skip-configs > "$OUT/bench_sq.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$R/bench.py" --full --skip-cpu --skip-configs > "$OUT/bench_stats.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --skip-cpu --skip-configs > "$OUT/bench_fetch.log" 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write" -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --skip-cpu --skip-configs > "$OUT/bench_write.log" 2>&1
+rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d "$OUT/sq" -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --skip-cpu --skip-configs > "$OUT/bench_sq.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/detector" -- python3 "$R/tools/bench_detector.py" > "$OUT/detector.log" 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, json, os, sys
@@ -33,12 +33,12 @@ bl = json.loads(line[-1])
 i0 = 1 + int(bl.get("settle_launches", 0)) + int(bl["warmup"])
 assert i0 + int(bl["steps"]) <= len(ms), f"{len(ms)} traced launches of {main[:40]}, the timed window ends at {i0 + int(bl['steps'])}"
 timed = ms[i0:i0 + int(bl["steps"])]
-json.dump({"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --skip-cpu   (1 set-up + settle + warm-up + timed Raytracer.trace calls, then raw launches + 1; counts in bench_line)",
+json.dump({"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --skip-cpu --skip-configs   (1 set-up + settle + warm-up + timed Raytracer.trace calls, then raw launches + 1; counts in bench_line)",
            "timed_launch_index_range": [i0, i0 + int(bl["steps"])],
            "kernel": rows[0]["Kernel_Name"][:40], "launch_ms": ms, "timed_mean_ms": sum(timed) / len(timed),
            "bench_line": bl}, open(os.path.join(out, "trace_kernel_launches.json"), "w"), indent=1)
 pmc = {"rays": 10000000, "pol": True, "unit": "KB per launch",
-       "command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --kernel-trace --output-format csv -- python3 bench.py --steps 3 --warmup 1 --skip-cpu"}
+       "command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --kernel-trace --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --skip-cpu --skip-configs"}
 for name, d in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
     rows = [r for r in csv.DictReader(open(newest(d + "/*/*_counter_collection.csv"))) if r["Kernel_Name"] == main and r["Counter_Name"] == name]
     vals = [float(r["Counter_Value"]) for r in rows]
