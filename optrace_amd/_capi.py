@@ -37,6 +37,17 @@ N_INFOS = 5
 PROJECTIONS = {None: PROJ_NONE, "Equidistant": PROJ_EQUIDISTANT, "Orthographic": PROJ_ORTHOGRAPHIC,
                "Equal-Area": PROJ_EQUAL_AREA, "Stereographic": PROJ_STEREOGRAPHIC}
 
+
+# The one routing rule of the detector stage (ot_api.hip numeric_hit / fused_ok, the same definition): the fused kernels serve
+# detectors with a closed-form hit (flat or conic) and no sphere projection with transcendentals.
+def numeric_hit(surf) -> bool:
+    """The detector's hit needs the numeric search (aspheric, tilted, spline surfaces)."""
+    return not (surf.kind == SURF_CONIC or surf.z_min == surf.z_max)
+
+
+def fused_ok(surf, projection: int) -> bool:
+    return not numeric_hit(surf) and projection in (PROJ_NONE, PROJ_ORTHOGRAPHIC)
+
 d3 = C.c_double * 3
 d2 = C.c_double * 2
 

@@ -9,6 +9,7 @@
 #include <string>
 #include <algorithm>
 #include <memory>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -1399,6 +1400,14 @@ extern "C" int ot_refraction_index(const ot_medium* medium, const double* table_
 enum { OT_WS_RENDER = 0, OT_WS_FUSED = 1, OT_WS_FUSED_HITS = 2, OT_WS_AUTO = 3, OT_WS_DET = 4 };
 static ot_scratch::Lease workspace(int purpose, size_t bytes, hipStream_t st);
 
+// The one routing rule of the detector stage (detector.py uses the same, _capi.fused_ok): the fused kernels of
+// ot_detector_images serve detectors with a closed-form hit (flat or conic) and no sphere projection with transcendentals;
+// every other request takes the chain ot_detector_hits_multi + render_accumulate.
+static bool numeric_hit(const ot_surface& s) { return !(s.kind == OT_SURF_CONIC || s.z_min == s.z_max); }
+static bool fused_ok(const ot_surface& s, int32_t projection) {
+    return !numeric_hit(s) && (projection == OT_PROJ_NONE || projection == OT_PROJ_ORTHOGRAPHIC);
+}
+
 extern "C" int ot_detector_hits_multi(const ot_rays* rays, int64_t first, int64_t count, const ot_detector_req* reqs,
                                       int32_t n_reqs, void* stream) {
     if (!rays || !reqs || n_reqs < 1) return fail(OT_ERR_INVALID, "ot_detector_hits: null argument");
@@ -1452,7 +1461,7 @@ extern "C" int ot_detector_hits_multi(const ot_rays* rays, int64_t first, int64_
         d.fill = reqs[k].fill;
         d.piece_shift = hit_piece_shift(count);
         if (reqs[k].extent4) d.ext_slots = slots + (size_t)4 * OT_EXT_SLOTS * e++;
-        numeric = numeric || !(d.det.kind == OT_SURF_CONIC || d.det.flat);
+        numeric = numeric || numeric_hit(*reqs[k].detector);
     }
     hipError_t err = hipSuccess;
     if (n_reqs > 1) err = hipMemcpyAsync(scratch, host.data(), sizeof(DetOne) * n_reqs, hipMemcpyHostToDevice, st);
@@ -1574,6 +1583,103 @@ extern "C" int ot_scratch_stats(int64_t* kept_bytes, int32_t* blocks, int32_t* l
 
 #define OT_TILE_MIN_HITS (1ll << 21)  // shorter lists: the direct kernel alone
 
+static int cu_count() {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+        return prop.multiProcessorCount;
+    return 256;
+}
+
+// ---- shared set-up of the binning paths ----------------------------------------------------------------------
+#define OT_PROBE_LDS (OT_TILE_PROBE_SET * (int)sizeof(int))
+#define OT_ACCUM_LDS ((OT_TILE_PX * 4 + OT_OBS_N * 6) * (int)sizeof(double))  // tile + (value, difference) observer table
+
+// One-time set-up per device, for the whole process: the dynamic-LDS limits of the binning kernels (hipFuncSetAttribute sets
+// a property of the function on the current device, not one of the calling thread) and the CIE observer table.  Marked done
+// only when every step has succeeded, so that a failure is reported again by the next call.
+static int detector_setup(const double** table) {
+    struct PerDevice {
+        bool done = false;
+        double* table = nullptr;
+    };
+    static std::mutex mu;
+    static PerDevice devs[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail(OT_ERR_HIP, "could not upload the CIE observer table");
+    std::lock_guard<std::mutex> lock(mu);
+    PerDevice& d = devs[dev];
+    if (!d.done) {
+        if (!d.table) {
+            // the 471 x 3 table, and behind it the same as (value, difference to the next row) pairs: 471 x 6 (observer_xyz_at6)
+            std::vector<double> both((size_t)OT_OBS_N * 9);
+            const double* src = (const double*)ot_observer_xyz;
+            for (int i = 0; i < OT_OBS_N * 3; i++) both[i] = src[i];
+            double* pairs = both.data() + (size_t)OT_OBS_N * 3;
+            for (int j = 0; j < OT_OBS_N; j++)
+                for (int c = 0; c < 3; c++) {
+                    pairs[6 * j + 2 * c] = src[3 * j + c];
+                    pairs[6 * j + 2 * c + 1] = (j + 1 < OT_OBS_N) ? (src[3 * (j + 1) + c] - src[3 * j + c]) / 1.0 : 0.0;  // observers.py:14-41
+                }
+            double* t = nullptr;
+            if (hipMalloc((void**)&t, sizeof(double) * both.size()) != hipSuccess) return fail(OT_ERR_HIP, "could not upload the CIE observer table");
+            if (hipMemcpy(t, both.data(), sizeof(double) * both.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipFree(t);
+                return fail(OT_ERR_HIP, "could not upload the CIE observer table");
+            }
+            d.table = t;
+        }
+        HIP_TRY(hipFuncSetAttribute((const void*)tile_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_PROBE_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void*)tile_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_ACCUM_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void*)fuse_accum_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_ACCUM_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void*)spec_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_ACCUM_LDS));
+        // the one-detector tile kernels stage their records in LDS: with many tiles more than the 64 KB a kernel gets unasked
+        const int most = 96 * 1024, lb = (int)fuse_lb_lds(OT_LB_MAXK);
+        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_lb_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
+        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_lb_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
+        d.done = true;
+    }
+    *table = d.table;
+    return OT_OK;
+}
+
+// OT_RENDER_PATH = direct | tiles pins the binning path (tests, profiling); unset: by hit count and probe
+struct RenderPath {
+    bool direct, tiles;
+};
+static RenderPath render_path() {
+    const char* pin = std::getenv("OT_RENDER_PATH");
+    return {pin && !std::strcmp(pin, "direct"), pin && !std::strcmp(pin, "tiles")};
+}
+
+// scratch layout: consecutive arrays, each on a 256-byte boundary
+struct Carver {
+    size_t off;
+    size_t operator()(size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes);
+        return o;
+    }
+};
+
+static RenderArgs render_args(const double extent[4], int32_t Nx, int32_t Ny, double ws) {
+    RenderArgs a;
+    a.x0 = extent[0];
+    a.x1 = extent[1];
+    a.y0 = extent[2];
+    a.y1 = extent[3];
+    a.fx = (double)Nx / (extent[1] - extent[0]);  // Nx / s[0]  misc.py:75
+    a.fy = (double)Ny / (extent[3] - extent[2]);
+    a.Nx = Nx;
+    a.Ny = Ny;
+    a.ws = ws;
+    return a;
+}
+
 static int render_accumulate(int64_t n, const unsigned int* fill, const double* px, const double* py, const float* w,
                              const float* wl, const double extent[4], int32_t Nx, int32_t Ny, double* hist, void* stream,
                              double weight_scale = 1.0);
@@ -1597,30 +1703,14 @@ static int render_accumulate(int64_t n, const unsigned int* fill, const double* 
         return fail(OT_ERR_INVALID, "ot_render_accumulate: bad argument");
     if (int rc = require_device()) return rc;
     if (n == 0) return OT_OK;
-    RenderArgs a;
-    a.x0 = extent[0];
-    a.y0 = extent[2];
-    a.x1 = extent[1];
-    a.y1 = extent[3];
-    a.fx = (double)Nx / (extent[1] - extent[0]);  // Nx / s[0]  misc.py:75
-    a.fy = (double)Ny / (extent[3] - extent[2]);
-    a.Nx = Nx;
-    a.Ny = Ny;
-    a.ws = weight_scale;
-    const double* table = observer_table_device();
-    if (!table) return fail(OT_ERR_HIP, "could not upload the CIE observer table");
+    const RenderArgs a = render_args(extent, Nx, Ny, weight_scale);
+    const double* table = nullptr;
+    if (int rc = detector_setup(&table)) return rc;
     // one 1024-thread workgroup per CU (grid-stride): LDS-privatised histogram, see render_kernel
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        cus = prop.multiProcessorCount;
-    int64_t blocks = (n + 1023) / 1024;
-    if (blocks > cus) blocks = cus;
+    const int64_t blocks = std::min<int64_t>((n + 1023) / 1024, cu_count());
     hipStream_t st = (hipStream_t)stream;
-    // OT_RENDER_PATH = direct | tiles pins the path (tests, profiling); default: by list length and probe
-    const char* pin = std::getenv("OT_RENDER_PATH");
-    const bool pin_direct = pin && !std::strcmp(pin, "direct"), pin_tiles = pin && !std::strcmp(pin, "tiles");
-    if (pin_direct || (n < OT_TILE_MIN_HITS && !pin_tiles)) {
+    const RenderPath pin = render_path();
+    if (pin.direct || (n < OT_TILE_MIN_HITS && !pin.tiles)) {
         hipLaunchKernelGGL(render_kernel, dim3((unsigned)blocks), dim3(1024), 0, st, n, px, py, w, wl, a, table, hist, (const int*)nullptr, fill);
         HIP_TRY(hipGetLastError());
         return OT_OK;
@@ -1642,12 +1732,7 @@ static int render_accumulate(int64_t n, const unsigned int* fill, const double* 
     t.chunk = ((n + 1023) / 1024 + 1023) / 1024 * 1024;
     if (t.chunk < 16384) t.chunk = 16384;
     t.max_chunks = (int32_t)(n / t.chunk + t.K + 1);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off = (off + bytes + 255) / 256 * 256;
-        return o;
-    };
+    Carver carve{0};
     const size_t o_spread = carve(sizeof(int));
     const size_t o_counts = carve(sizeof(unsigned int) * OT_TILE_PIECES * (size_t)t.K);
     const size_t o_tot = carve(sizeof(unsigned long long) * t.K);
@@ -1655,7 +1740,7 @@ static int render_accumulate(int64_t n, const unsigned int* fill, const double* 
     const size_t o_cstart = carve(sizeof(int) * (t.K + 1));
     const size_t o_rec = carve(sizeof(TileRec) * (size_t)n);
     const size_t o_slabs = carve(sizeof(double) * OT_TILE_PX * 4 * (size_t)t.max_chunks);
-    const ot_scratch::Lease lease = workspace(OT_WS_RENDER, off, st);
+    const ot_scratch::Lease lease = workspace(OT_WS_RENDER, carve.off, st);
     char* ws = lease.p();
     if (!ws) {
         // no room for the hit records (12 B per hit): the direct kernel needs no scratch
@@ -1672,24 +1757,16 @@ static int render_accumulate(int64_t n, const unsigned int* fill, const double* 
     wk.chunk_start = (int*)(ws + o_cstart);
     wk.rec = (TileRec*)(ws + o_rec);
     wk.slabs = (double*)(ws + o_slabs);
-    const int lds_probe = OT_TILE_PROBE_SET * (int)sizeof(int);
-    const int lds_accum = (OT_TILE_PX * 4 + OT_OBS_N * 6) * (int)sizeof(double);  // tile + (value, difference) observer table
-    static thread_local bool lds_set[64] = {false};
-    if (dev >= 0 && dev < 64 && !lds_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)tile_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_probe));
-        HIP_TRY(hipFuncSetAttribute((const void*)tile_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_accum));
-        lds_set[dev] = true;
-    }
-    if (pin_tiles)
+    if (pin.tiles)
         HIP_TRY(hipMemsetAsync(wk.spread, 1, sizeof(int), st));
     else
-        hipLaunchKernelGGL(tile_probe_kernel, dim3(1), dim3(1024), lds_probe, st, t, px, py, w, wk.spread, fill);
+        hipLaunchKernelGGL(tile_probe_kernel, dim3(1), dim3(1024), OT_PROBE_LDS, st, t, px, py, w, wk.spread, fill);
     hipLaunchKernelGGL(render_kernel, dim3((unsigned)blocks), dim3(1024), 0, st, n, px, py, w, wl, a, table, hist, (const int*)wk.spread, fill);
     hipLaunchKernelGGL(tile_count_kernel, dim3(OT_TILE_PIECES), dim3(1024), 0, st, t, px, py, w, wk);
     hipLaunchKernelGGL(tile_cursor_kernel, dim3((unsigned)((t.K + 3) / 4)), dim3(256), 0, st, t, wk, wk.tot);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, st, t, wk, (const unsigned long long*)wk.tot);
     hipLaunchKernelGGL(tile_scatter_kernel, dim3(OT_TILE_PIECES), dim3(1024), 0, st, t, px, py, w, wl, wk);
-    hipLaunchKernelGGL(tile_accum_kernel, dim3((unsigned)t.max_chunks), dim3(1024), lds_accum, st, t, table, wk);
+    hipLaunchKernelGGL(tile_accum_kernel, dim3((unsigned)t.max_chunks), dim3(1024), OT_ACCUM_LDS, st, t, table, wk);
     hipLaunchKernelGGL(tile_reduce_kernel, dim3(OT_TILE_PX / 256, (unsigned)t.K), dim3(256), 0, st, t, wk, hist);
     HIP_TRY(hipGetLastError());
     return OT_OK;
@@ -1706,29 +1783,93 @@ struct FuseIndexAll {
     FuseIndex v[OT_DET_MAX];
 };
 
-static int cu_count();
-
 // one detector, an image of few tiles: the tile kernel with line buffers (OT_TILE_LINEBUF=0 in the environment: the plain one)
 static bool fuse_use_linebuf(int K) {
     const char* v = std::getenv("OT_TILE_LINEBUF");
     return K <= OT_LB_MAXK && !(v && v[0] == '0');
 }
 
-// the one-detector tile kernels stage their records in LDS: with many tiles more than the 64 KB a kernel gets unasked
-static int fuse_tiles_allow_lds(int dev) {
-    static thread_local bool done[64] = {false};
-    if (dev < 0 || dev >= 64 || done[dev]) return OT_OK;
-    const int most = 96 * 1024;
-    HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<false, 1, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<false, 1, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<false, 1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<false, 1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    const int lb = (int)fuse_lb_lds(OT_LB_MAXK);
-    HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_lb_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-    HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_lb_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-    done[dev] = true;
-    return OT_OK;
+static int tile_count(int32_t Nx, int32_t Ny) { return ((Nx + OT_TILE_W - 1) / OT_TILE_W) * ((Ny + OT_TILE_W - 1) / OT_TILE_W); }
+
+// the rays from `first` on as a storage of their own: the tile kernels address their rays with 32 bits from its start
+static ot_rays rays_from(const ot_rays& rays, int64_t first) {
+    ot_rays part = rays;
+    part.p += first;
+    part.w += first;
+    part.wl += first;
+    return part;
 }
+
+// Shape of the tile kernel's launch: n_wg persistent workgroups of `piece` rays.  A workgroup hands out chunks of its own
+// part of a detector's pool (per_wg chunks); every (workgroup, tile) pair leaves at most one chunk partly filled.
+// small_k: two rays per thread and sub-block (images of at most 1024 tiles: 10-bit tile numbers); linebuf: the line-buffer
+// kernel, one 1024-thread workgroup per CU.
+struct TilePool {
+    unsigned n_wg;
+    int64_t piece;
+    TilePool(int64_t count, bool linebuf, bool small_k, int cus) {
+        const int64_t brt = linebuf ? OT_LB_BR * OT_LB_RPT : OT_FUSE_BR * (small_k ? 2 : 1);
+        n_wg = (unsigned)std::min<int64_t>((linebuf ? 1 : OT_FUSE_WG_PER_CU) * (int64_t)cus, (count + brt - 1) / brt);
+        piece = ((count + n_wg - 1) / n_wg + brt - 1) / brt * brt;
+    }
+    void size(FuseOne& f) const {  // (f.K set)
+        f.per_wg = (uint32_t)((piece + OT_FUSE_CH - 1) / OT_FUSE_CH + f.K + 2);
+        f.cap = (uint32_t)std::min<int64_t>((int64_t)f.per_wg * n_wg, 0xffffffffll / OT_FUSE_CH - 1);  // record numbers: 32 bits
+    }
+};
+
+// Scratch of the second tile pass for n detectors of at most K tiles and cap chunks each: chunks grouped by tile (FuseIndex),
+// and one slab per accumulation workgroup -- a tile with c chunks takes ceil(c / OT_FUSE_CPW) of them
+struct IndexLayout {
+    size_t o_tn, o_ts, o_list, o_ws, o_slabs;
+    int K;
+    uint32_t cap;
+    unsigned n_slabs;
+    IndexLayout() = default;
+    IndexLayout(Carver& carve, int K_, uint32_t cap_, int n) : K(K_), cap(cap_) {
+        o_tn = carve(sizeof(unsigned int) * K * (size_t)n);
+        o_ts = carve(sizeof(unsigned int) * (K + 1) * (size_t)n);
+        o_list = carve(sizeof(unsigned int) * (size_t)cap * n);
+        o_ws = carve(sizeof(unsigned int) * (K + 1) * (size_t)n);
+        n_slabs = (unsigned)((cap + OT_FUSE_CPW - 1) / OT_FUSE_CPW) + (unsigned)K;
+        o_slabs = carve(sizeof(double) * OT_TILE_PX * 4 * (size_t)n_slabs * n);
+    }
+    FuseIndex at(char* ws, int k) const {
+        FuseIndex ix{};
+        ix.tile_n = (unsigned int*)(ws + o_tn) + (size_t)K * k;
+        ix.tstart = (unsigned int*)(ws + o_ts) + (size_t)(K + 1) * k;
+        ix.wstart = (unsigned int*)(ws + o_ws) + (size_t)(K + 1) * k;
+        ix.n_slabs = n_slabs;
+        ix.list = (unsigned int*)(ws + o_list) + (size_t)cap * k;
+        ix.slabs = (double*)(ws + o_slabs) + (size_t)OT_TILE_PX * 4 * n_slabs * k;
+        return ix;
+    }
+};
+
+// the launches of ot_detector_images' first pass: the direct kernel, and the tile kernel where a detector has a pool
+struct FusedPass {
+    const ot_rays& rays;
+    int64_t first, count;
+    const FuseOne* dd;
+    int n_reqs, KT;
+    const double* table;
+    unsigned blocks;
+    const TilePool& tp;
+    hipStream_t st;
+    template <int NDET, int RPT, bool PAIR>
+    void launch() const {
+        hipLaunchKernelGGL((fuse_direct_kernel<NDET>), dim3(blocks), dim3(1024), 0, st, rays, first, count, dd, n_reqs, table);
+        if (KT)
+            hipLaunchKernelGGL((fuse_tiles_kernel<NDET, RPT, false, PAIR>), dim3(tp.n_wg), dim3(OT_FUSE_BR), fuse_tiles_lds(KT), st,
+                               rays_from(rays, first), (uint32_t)count, dd, n_reqs, KT, (uint32_t)tp.piece);
+    }
+    template <bool PAIR>
+    void launch_multi() const {  // (unused entries of the unrolled detector loop cost registers: the smallest NDET that fits)
+        if (n_reqs <= 2) launch<2, 1, PAIR>();
+        else if (n_reqs <= 4) launch<4, 1, PAIR>();
+        else launch<8, 1, PAIR>();
+    }
+};
 
 extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t count, const ot_detector_image_req* reqs,
                                   int32_t n_reqs, void* stream) {
@@ -1755,9 +1896,7 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
     // kernels need every vector register there is and lose to hit search + binning (C3, 5e7 rays: 3.1 against 2.1 ms).
     for (int k = 0; k < n_reqs; k++) {
         const ot_detector_image_req& q = reqs[k];
-        const bool closed = q.detector->kind <= OT_SURF_CONIC || q.detector->z_min == q.detector->z_max;
-        const bool plain = q.projection == OT_PROJ_NONE || q.projection == OT_PROJ_ORTHOGRAPHIC;
-        if (closed && plain) continue;
+        if (fused_ok(*q.detector, q.projection)) continue;
         // this request alone through ot_detector_hits + ot_render_accumulate, the others through the fused kernels
         const size_t o_hw = align_up(sizeof(double) * 2 * (size_t)count);
         const ot_scratch::Lease hits = workspace(OT_WS_FUSED_HITS, o_hw + sizeof(float) * (size_t)count, st);
@@ -1783,48 +1922,32 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
             if (j != k) rest.push_back(reqs[j]);
         return rest.empty() ? OT_OK : ot_detector_images(rays, first, count, rest.data(), (int32_t)rest.size(), stream);
     }
-    const double* table = observer_table_device();
-    if (!table) return fail(OT_ERR_HIP, "could not upload the CIE observer table");
-    int dev = 0;
-    (void)hipGetDevice(&dev);
+    // from here on every request has a closed-form hit and no sphere projection
+    const double* table = nullptr;
+    if (int rc = detector_setup(&table)) return rc;
     const int cus = cu_count();
     // a tile-kernel workgroup keeps 20 B of LDS per (detector, tile): more tiles than fit -> two calls
     int KT_all = 0;
-    for (int k = 0; k < n_reqs; k++)
-        KT_all += ((reqs[k].Nx + OT_TILE_W - 1) / OT_TILE_W) * ((reqs[k].Ny + OT_TILE_W - 1) / OT_TILE_W);
+    for (int k = 0; k < n_reqs; k++) KT_all += tile_count(reqs[k].Nx, reqs[k].Ny);
     if (n_reqs > 1 && KT_all > OT_FUSE_LDS_ENTRIES) {
         const int h = n_reqs / 2;
         if (int rc = ot_detector_images(rays, first, count, reqs, h, stream)) return rc;
         return ot_detector_images(rays, first, count, reqs + h, n_reqs - h, stream);
     }
-    // OT_RENDER_PATH = direct | tiles pins the binning path (tests, profiling); default: by ray count and probe
-    const char* pin = std::getenv("OT_RENDER_PATH");
-    const bool pin_direct = pin && !std::strcmp(pin, "direct"), pin_tiles = pin && !std::strcmp(pin, "tiles");
+    const RenderPath pin = render_path();
     // (the threshold counts the hits a call may bin: rays x detectors -- the last, short chunk of an iterative render with six
     // positions then stays on the tile path instead of 6e6 global atomic quadruples)
-    const bool want_tiles = !pin_direct && (pin_tiles || count * (int64_t)n_reqs >= OT_TILE_MIN_HITS);
+    const bool want_tiles = !pin.direct && (pin.tiles || count * (int64_t)n_reqs >= OT_TILE_MIN_HITS);
     if (count >= (1ll << 31)) return fail(OT_ERR_UNSUPPORTED, "ot_detector_images: at most 2^31 - 1 rays per call");
-    // tile kernel: two rays per thread and sub-block where the images have at most 1024 tiles (10-bit tile numbers)
     bool small_k = n_reqs == 1;
-    for (int k = 0; k < n_reqs; k++)
-        small_k = small_k && ((reqs[k].Nx + OT_TILE_W - 1) / OT_TILE_W) * ((reqs[k].Ny + OT_TILE_W - 1) / OT_TILE_W) <= 1024;
-    // one detector with a closed-form hit and an image of few tiles: the kernel with line buffers, one 1024-thread workgroup per CU
-    // (every request that reaches this point has a closed-form hit and no sphere projection)
-    const bool linebuf = n_reqs == 1 && fuse_use_linebuf(((reqs[0].Nx + OT_TILE_W - 1) / OT_TILE_W) * ((reqs[0].Ny + OT_TILE_W - 1) / OT_TILE_W));
-    const int64_t brt = linebuf ? OT_LB_BR * OT_LB_RPT : OT_FUSE_BR * (small_k ? 2 : 1);
-    const unsigned n_wg = (unsigned)std::min<int64_t>((linebuf ? 1 : OT_FUSE_WG_PER_CU) * (int64_t)cus, (count + brt - 1) / brt);
-    const int64_t piece = ((count + n_wg - 1) / n_wg + brt - 1) / brt * brt;
+    for (int k = 0; k < n_reqs; k++) small_k = small_k && tile_count(reqs[k].Nx, reqs[k].Ny) <= 1024;
+    const bool linebuf = n_reqs == 1 && fuse_use_linebuf(tile_count(reqs[0].Nx, reqs[0].Ny));
+    const TilePool tp(count, linebuf, small_k, cus);
 
     std::vector<FuseOne> host(n_reqs);
-    bool numeric = false, general = false;  // general: numeric hit search or a sphere projection somewhere
     int KT = 0, Kmax = 1;
     uint32_t capmax = 1;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off = (off + bytes + 255) / 256 * 256;
-        return o;
-    };
+    Carver carve{0};
     const size_t o_dets = carve(sizeof(FuseOne) * n_reqs);
     const size_t o_flags = carve(sizeof(int) * 4 * n_reqs);  // per detector: spread, -, overflow, pad
     const size_t o_pcnt = carve(sizeof(int) * 2 * n_reqs);   // probe: distinct pixels, workgroups done
@@ -1838,57 +1961,36 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
         f.Rcurv = q.detector->R;
         if (q.crop4) f.crop = {q.crop4[0], q.crop4[1], q.crop4[2], q.crop4[3], 1};
         f.projection = q.projection;
-        f.a.x0 = q.extent[0];
-        f.a.x1 = q.extent[1];
-        f.a.y0 = q.extent[2];
-        f.a.y1 = q.extent[3];
-        f.a.fx = (double)q.Nx / (q.extent[1] - q.extent[0]);  // Nx / s[0]  misc.py:75
-        f.a.fy = (double)q.Ny / (q.extent[3] - q.extent[2]);
-        f.a.Nx = q.Nx;
-        f.a.Ny = q.Ny;
-        f.a.ws = q.weight_scale;
+        f.a = render_args(q.extent, q.Nx, q.Ny, q.weight_scale);
         f.tx = (q.Nx + OT_TILE_W - 1) / OT_TILE_W;
-        f.K = f.tx * ((q.Ny + OT_TILE_W - 1) / OT_TILE_W);
+        f.K = tile_count(q.Nx, q.Ny);
         f.ill = (unsigned long long*)q.ill_count;
         f.hist = q.hist;
         f.tiles_ok = want_tiles && f.K <= OT_TILE_MAX && f.K <= OT_FUSE_LDS_ENTRIES;
         f.koff = KT;
         if (f.tiles_ok) {
             KT += f.K;
-            // a workgroup hands out chunks of its own part of the pool; every (workgroup, tile) pair leaves at most one
-            // chunk partly filled
-            f.per_wg = (uint32_t)((piece + OT_FUSE_CH - 1) / OT_FUSE_CH + f.K + 2);
-            f.cap = (uint32_t)std::min<int64_t>((int64_t)f.per_wg * n_wg, 0xffffffffll / OT_FUSE_CH - 1);  // record numbers: 32 bits
+            tp.size(f);
             o_ctile[k] = carve(sizeof(uint32_t) * f.cap);
             o_cfill[k] = carve(sizeof(uint32_t) * f.cap);
             o_rec[k] = carve(sizeof(TileRec) * (size_t)f.cap * OT_FUSE_CH);
             Kmax = std::max(Kmax, f.K);
             capmax = std::max(capmax, f.cap);
         }
-        numeric = numeric || !(f.det.kind == OT_SURF_CONIC || f.det.flat);
-        general = general || !(f.det.kind == OT_SURF_CONIC || f.det.flat) || (q.projection != OT_PROJ_NONE && q.projection != OT_PROJ_ORTHOGRAPHIC);
     }
     // second pass (chunks grouped by tile, accumulation, reduction): every detector its own index and slabs, so that one launch
     // per step serves them all (six positions of an iterative render: 400 accumulation workgroups each, 1.6 rounds over 256 CUs
     // when launched one after the other)
-    const int n_idx = KT ? n_reqs : 0;
     const size_t o_ixs = carve(sizeof(FuseIndexAll));
-    const size_t o_tn = carve(sizeof(unsigned int) * Kmax * (size_t)n_idx);
-    const size_t o_ts = carve(sizeof(unsigned int) * (Kmax + 1) * (size_t)n_idx);
-    const size_t o_list = carve(sizeof(unsigned int) * (size_t)capmax * n_idx);
-    const size_t o_ws = carve(sizeof(unsigned int) * (Kmax + 1) * (size_t)n_idx);
-    // one slab per accumulation workgroup: a tile with n chunks takes ceil(n / OT_FUSE_CPW) of them
-    const unsigned n_slabs = (unsigned)((capmax + OT_FUSE_CPW - 1) / OT_FUSE_CPW) + (unsigned)Kmax;
-    const size_t o_slabs = carve(sizeof(double) * OT_TILE_PX * 4 * (size_t)n_slabs * n_idx);
-    ot_scratch::Lease lease = workspace(OT_WS_FUSED, off, st);
+    const IndexLayout idx(carve, Kmax, capmax, KT ? n_reqs : 0);
+    ot_scratch::Lease lease = workspace(OT_WS_FUSED, carve.off, st);
     char* ws = lease.p();
     if (!ws) {
         if (!KT) return fail(OT_ERR_HIP, "ot_detector_images: no scratch memory");
         // no room for the records: bin directly (needs the flags and the detector table only)
         KT = 0;
         for (auto& f : host) f.tiles_ok = 0;
-        off = o_flags + sizeof(int) * 4 * n_reqs + 256;
-        lease = workspace(OT_WS_FUSED, off, st);
+        lease = workspace(OT_WS_FUSED, o_flags + sizeof(int) * 4 * n_reqs + 256, st);
         ws = lease.p();
         if (!ws) return fail(OT_ERR_HIP, "ot_detector_images: no scratch memory");
     }
@@ -1906,17 +2008,9 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
     hipError_t err = hipMemsetAsync(flags, 0, sizeof(int) * 4 * n_reqs, st);
     if (err == hipSuccess) err = hipMemcpyAsync(ws + o_dets, host.data(), sizeof(FuseOne) * n_reqs, hipMemcpyHostToDevice, st);
     const FuseOne* dd = (const FuseOne*)(ws + o_dets);
-    static thread_local bool lds_set[64] = {false};
-    const int lds_accum = (OT_TILE_PX * 4 + OT_OBS_N * 6) * (int)sizeof(double);  // tile + (value, difference) observer table
-    if (err == hipSuccess && dev >= 0 && dev < 64 && !lds_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_accum));
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_accum_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_accum));
-        lds_set[dev] = true;
-    }
-    if (int rc = fuse_tiles_allow_lds(dev)) return rc;
     if (err == hipSuccess) {
         if (KT) {
-            if (pin_tiles) {  // spread = 1 for every detector with a pool
+            if (pin.tiles) {  // spread = 1 for every detector with a pool
                 std::vector<int> hf(4 * n_reqs, 0);
                 for (int k = 0; k < n_reqs; k++) hf[4 * k] = host[k].tiles_ok;
                 err = hipMemcpyAsync(flags, hf.data(), sizeof(int) * 4 * n_reqs, hipMemcpyHostToDevice, st);
@@ -1927,67 +2021,29 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
                 err = hipMemsetAsync(pcnt, 0, sizeof(int) * 2 * n_reqs, st);
                 if (err == hipSuccess) err = hipMemsetAsync(pset, 0xff, sizeof(int) * OT_TILE_PROBE_SET * (size_t)n_reqs, st);
                 const dim3 pg(n_reqs, OT_TILE_PROBE / OT_FUSE_PROBE_WG);
-                if (numeric)
-                    hipLaunchKernelGGL(fuse_probe_kernel<true>, pg, dim3(OT_FUSE_PROBE_WG), 0, st, *rays, first, count, dd, pset, pcnt);
-                else
-                    hipLaunchKernelGGL(fuse_probe_kernel<false>, pg, dim3(OT_FUSE_PROBE_WG), 0, st, *rays, first, count, dd, pset, pcnt);
+                hipLaunchKernelGGL(fuse_probe_kernel, pg, dim3(OT_FUSE_PROBE_WG), 0, st, *rays, first, count, dd, pset, pcnt);
             }
         }
-        const unsigned blocks = (unsigned)std::min<int64_t>(cus, (count + 1023) / 1024);
-        const size_t lds_tiles = fuse_tiles_lds(KT, general ? 8 : (n_reqs == 1 ? 1 : 2), small_k ? 2 : 1, false);
-        ot_rays part = *rays;  // the tile kernel addresses its rays with 32 bits from the start of the range
-        part.p += first;
-        part.w += first;
-        part.wl += first;
-#define OT_LAUNCH_FUSE(NUM, ND, RP)                                                                                       \
-    do {                                                                                                                  \
-        hipLaunchKernelGGL((fuse_direct_kernel<NUM, ND>), dim3(blocks), dim3(1024), 0, st, *rays, first, count, dd, n_reqs, table); \
-        if (KT)                                                                                                           \
-            hipLaunchKernelGGL((fuse_tiles_kernel<NUM, ND, RP>), dim3(n_wg), dim3(OT_FUSE_BR), lds_tiles, st, part,        \
-                               (uint32_t)count, dd, n_reqs, KT, (uint32_t)piece);                                          \
-    } while (0)
-        if (general) {
-            OT_LAUNCH_FUSE(true, 8, 1);
-        } else if (linebuf) {
-            hipLaunchKernelGGL((fuse_direct_kernel<false, 1>), dim3(blocks), dim3(1024), 0, st, *rays, first, count, dd, n_reqs, table);
+        const FusedPass pass{*rays, first, count, dd, n_reqs, KT, table, (unsigned)std::min<int64_t>(cus, (count + 1023) / 1024), tp, st};
+        if (linebuf) {
+            hipLaunchKernelGGL((fuse_direct_kernel<1>), dim3(pass.blocks), dim3(1024), 0, st, *rays, first, count, dd, n_reqs, table);
             if (KT)
-                hipLaunchKernelGGL(fuse_tiles_lb_kernel<false>, dim3(n_wg), dim3(OT_LB_BR), fuse_lb_lds(KT), st, part, (uint32_t)count,
-                                   dd, KT, (uint32_t)piece);
+                hipLaunchKernelGGL(fuse_tiles_lb_kernel<false>, dim3(tp.n_wg), dim3(OT_LB_BR), fuse_lb_lds(KT), st, rays_from(*rays, first),
+                                   (uint32_t)count, dd, KT, (uint32_t)tp.piece);
         } else if (n_reqs == 1) {
-            if (small_k) OT_LAUNCH_FUSE(false, 1, 2); else OT_LAUNCH_FUSE(false, 1, 1);
+            if (small_k) pass.launch<1, 2, false>(); else pass.launch<1, 1, false>();
         } else if (rays->nt == 2) {  // two sections (a tail storage): every hit from the prefetched pair, no section search
-#define OT_LAUNCH_FUSE_PAIR(ND)                                                                                           \
-    do {                                                                                                                  \
-        hipLaunchKernelGGL((fuse_direct_kernel<false, ND>), dim3(blocks), dim3(1024), 0, st, *rays, first, count, dd, n_reqs, table); \
-        if (KT)                                                                                                           \
-            hipLaunchKernelGGL((fuse_tiles_kernel<false, ND, 1, false, true>), dim3(n_wg), dim3(OT_FUSE_BR), lds_tiles, st, part, \
-                               (uint32_t)count, dd, n_reqs, KT, (uint32_t)piece);                                          \
-    } while (0)
-            if (n_reqs <= 2) OT_LAUNCH_FUSE_PAIR(2); else if (n_reqs <= 4) OT_LAUNCH_FUSE_PAIR(4); else OT_LAUNCH_FUSE_PAIR(8);
-#undef OT_LAUNCH_FUSE_PAIR
-        } else if (n_reqs <= 2) {
-            OT_LAUNCH_FUSE(false, 2, 1);
-        } else if (n_reqs <= 4) {
-            OT_LAUNCH_FUSE(false, 4, 1);
+            pass.launch_multi<true>();
         } else {
-            OT_LAUNCH_FUSE(false, 8, 1);
+            pass.launch_multi<false>();
         }
-#undef OT_LAUNCH_FUSE
         err = hipGetLastError();
         // tile path, all detectors per launch: chunks grouped by tile, LDS accumulation, slabs summed into the images
         if (err == hipSuccess && KT) {
             FuseIndexAll ixs;
             std::memset(&ixs, 0, sizeof(ixs));
-            for (int k = 0; k < n_reqs; k++) {
-                FuseIndex& ix = ixs.v[k];
-                ix.tile_n = (unsigned int*)(ws + o_tn) + (size_t)Kmax * k;
-                ix.tstart = (unsigned int*)(ws + o_ts) + (size_t)(Kmax + 1) * k;
-                ix.wstart = (unsigned int*)(ws + o_ws) + (size_t)(Kmax + 1) * k;
-                ix.n_slabs = n_slabs;
-                ix.list = (unsigned int*)(ws + o_list) + (size_t)capmax * k;
-                ix.slabs = (double*)(ws + o_slabs) + (size_t)OT_TILE_PX * 4 * n_slabs * k;
-            }
-            err = hipMemsetAsync(ws + o_tn, 0, sizeof(unsigned int) * Kmax * (size_t)n_reqs, st);
+            for (int k = 0; k < n_reqs; k++) ixs.v[k] = idx.at(ws, k);
+            err = hipMemsetAsync(ws + idx.o_tn, 0, sizeof(unsigned int) * Kmax * (size_t)n_reqs, st);
             if (err == hipSuccess) {
                 hipLaunchKernelGGL(put_kernel<FuseIndexAll>, dim3(1), dim3(64), 0, st, ixs, (FuseIndexAll*)(ws + o_ixs));
                 const FuseIndex* dix = (const FuseIndex*)(ws + o_ixs);
@@ -1996,7 +2052,8 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
                 hipLaunchKernelGGL(fuse_chunk_hist_multi_kernel, dim3(gc, 1, nd), dim3(1024), 0, st, dd, dix);
                 hipLaunchKernelGGL(fuse_chunk_scan_multi_kernel, dim3(1, 1, nd), dim3(1024), 0, st, dd, dix);
                 hipLaunchKernelGGL(fuse_chunk_place_multi_kernel, dim3(gc, 1, nd), dim3(1024), 0, st, dd, dix);
-                hipLaunchKernelGGL(fuse_accum_multi_kernel, dim3(std::min<unsigned>(n_slabs, (unsigned)cus), 1, nd), dim3(1024), lds_accum, st, dd, dix, table);
+                hipLaunchKernelGGL(fuse_accum_multi_kernel, dim3(std::min<unsigned>(idx.n_slabs, (unsigned)cus), 1, nd), dim3(1024), OT_ACCUM_LDS, st,
+                                   dd, dix, table);
                 hipLaunchKernelGGL(fuse_reduce_multi_kernel, dim3(OT_TILE_PX / 256, (unsigned)Kmax, nd), dim3(256), 0, st, dd, dix);
                 err = hipGetLastError();
             }
@@ -2022,10 +2079,8 @@ struct ot_auto_image {
     FuseOne f;  // host copy; the image grid (a, hist) is filled in by finish
     ot_scratch::Lease lease;  // the records: leased until finish / cancel (neither reused nor trimmed in between)
     char* ws;
-    size_t o_tn, o_ts, o_list, o_ws, o_slabs;
-    unsigned n_slabs;
+    IndexLayout idx;
     hipStream_t st;
-    int dev;
 };
 
 static int auto_detector(const char* who, const ot_rays* rays, int64_t first, int64_t count, const ot_surface* detector,
@@ -2034,9 +2089,7 @@ static int auto_detector(const char* who, const ot_rays* rays, int64_t first, in
     if (!rays->p || !rays->w || !rays->wl) return fail(OT_ERR_INVALID, std::string(who) + ": ray storage has null buffers");
     if (first < 0 || count < 1 || first + count > rays->N) return fail(OT_ERR_INVALID, std::string(who) + ": range outside the storage");
     if (count >= (1ll << 31)) return fail(OT_ERR_UNSUPPORTED, std::string(who) + ": at most 2^31 - 1 rays per call");
-    const bool closed = detector->kind <= OT_SURF_CONIC || detector->z_min == detector->z_max;
-    const bool plain = projection == OT_PROJ_NONE || projection == OT_PROJ_ORTHOGRAPHIC;
-    if (!closed || !plain)
+    if (!fused_ok(*detector, projection))
         return fail(OT_ERR_UNSUPPORTED, std::string(who) + ": detectors with a numeric hit search or a sphere projection take ot_detector_hits_multi");
     return OT_OK;
 }
@@ -2065,12 +2118,8 @@ extern "C" int ot_detector_extent_sample(const ot_rays* rays, int64_t first, int
     f.g.ext_slots = (unsigned long long*)(ws + h.o_slots);
     hipLaunchKernelGGL(put_kernel<FuseOne>, dim3(1), dim3(64), 0, st, f, (FuseOne*)(ws + h.o_dets));
     hipLaunchKernelGGL(extent_init_kernel, dim3(1), dim3(4 * OT_EXT_SLOTS), 0, st, f.g.ext_slots);
-    ot_rays part = *rays;
-    part.p += first;
-    part.w += first;
-    part.wl += first;
     const int64_t waves = (count + 64ll * stride - 1) / (64ll * stride);
-    hipLaunchKernelGGL(spec_sample_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, part, (uint32_t)count,
+    hipLaunchKernelGGL(spec_sample_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rays_from(*rays, first), (uint32_t)count,
                        (const FuseOne*)(ws + h.o_dets), (uint32_t)stride);
     hipLaunchKernelGGL(spec_result_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)f.g.ext_slots,
                        (const unsigned int*)nullptr, 0u, extent4);
@@ -2093,12 +2142,8 @@ extern "C" int ot_detector_image_auto_begin(const ot_rays* rays, int64_t first, 
     hipStream_t st = (hipStream_t)stream;
     LeafSurface ls;
     if (int rc = ls.init(detector, st)) return rc;
-    const int cus = cu_count();
-    const bool small_k = K <= 1024;  // two rays per thread and sub-block (10-bit tile numbers), as in ot_detector_images
-    const bool linebuf = fuse_use_linebuf((int)K);  // few tiles: line buffers, one 1024-thread workgroup per CU
-    const int64_t brt = linebuf ? OT_LB_BR * OT_LB_RPT : OT_FUSE_BR * (small_k ? 2 : 1);
-    const unsigned n_wg = (unsigned)std::min<int64_t>((linebuf ? 1 : OT_FUSE_WG_PER_CU) * (int64_t)cus, (count + brt - 1) / brt);
-    const int64_t piece = ((count + n_wg - 1) / n_wg + brt - 1) / brt * brt;
+    const bool small_k = K <= 1024, linebuf = fuse_use_linebuf((int)K);  // as in ot_detector_images
+    const TilePool tp(count, linebuf, small_k, cu_count());
 
     std::unique_ptr<ot_auto_image> im(new ot_auto_image);
     FuseOne& f = im->f;
@@ -2107,8 +2152,7 @@ extern "C" int ot_detector_image_auto_begin(const ot_rays* rays, int64_t first, 
     f.K = (int32_t)K;
     f.tiles_ok = 1;
     f.koff = 0;
-    f.per_wg = (uint32_t)((piece + OT_FUSE_CH - 1) / OT_FUSE_CH + f.K + 2);
-    f.cap = (uint32_t)std::min<int64_t>((int64_t)f.per_wg * n_wg, 0xffffffffll / OT_FUSE_CH - 1);  // record numbers: 32 bits
+    tp.size(f);
     f.g.X0 = origin[0];
     f.g.Y0 = origin[1];
     f.g.tw = tile[0];
@@ -2120,29 +2164,19 @@ extern "C" int ot_detector_image_auto_begin(const ot_rays* rays, int64_t first, 
     f.g.esc_cap = (unsigned int)std::max<int64_t>(1ll << 18, count / 64);
 
     const AutoHead h;
-    size_t off = h.end;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off = (off + bytes + 255) / 256 * 256;
-        return o;
-    };
+    Carver carve{h.end};
     const size_t o_ctile = carve(sizeof(uint32_t) * f.cap);
     const size_t o_cfill = carve(sizeof(uint32_t) * f.cap);
     const size_t o_rec = carve(sizeof(SpecRec) * (size_t)f.cap * OT_FUSE_CH);
     const size_t o_esc = carve(sizeof(SpecRec) * (size_t)f.g.esc_cap);
-    im->o_tn = carve(sizeof(unsigned int) * f.K);
-    im->o_ts = carve(sizeof(unsigned int) * (f.K + 1));
-    im->o_list = carve(sizeof(unsigned int) * f.cap);
-    im->o_ws = carve(sizeof(unsigned int) * (f.K + 1));
-    im->n_slabs = (unsigned)((f.cap + OT_FUSE_CPW - 1) / OT_FUSE_CPW) + (unsigned)f.K;
-    im->o_slabs = carve(sizeof(double) * OT_TILE_PX * 4 * (size_t)im->n_slabs);
-    im->lease = workspace(OT_WS_AUTO, off, st);
+    im->idx = IndexLayout(carve, f.K, f.cap, 1);
+    im->lease = workspace(OT_WS_AUTO, carve.off, st);
     char* ws = im->lease.p();
     if (!ws) return fail(OT_ERR_UNSUPPORTED, "ot_detector_image_auto_begin: no memory for the records (take the hit-list path)");
     im->ws = ws;
     im->st = st;
-    (void)hipGetDevice(&im->dev);
-    if (int rc = fuse_tiles_allow_lds(im->dev)) return rc;
+    const double* table = nullptr;
+    if (int rc = detector_setup(&table)) return rc;
     int* flags = (int*)(ws + h.o_flags);
     f.spread = flags;
     f.overflow = flags + 2;
@@ -2155,21 +2189,17 @@ extern "C" int ot_detector_image_auto_begin(const ot_rays* rays, int64_t first, 
     hipLaunchKernelGGL(put_kernel<int4>, dim3(1), dim3(64), 0, st, make_int4(1, 0, 0, 0), (int4*)flags);  // spread = 1: tiles always
     hipLaunchKernelGGL(put_kernel<FuseOne>, dim3(1), dim3(64), 0, st, f, (FuseOne*)(ws + h.o_dets));
     hipLaunchKernelGGL(extent_init_kernel, dim3(1), dim3(4 * OT_EXT_SLOTS), 0, st, f.g.ext_slots);
-    ot_rays part = *rays;  // the tile kernel addresses its rays with 32 bits from the start of the range
-    part.p += first;
-    part.w += first;
-    part.wl += first;
+    const ot_rays part = rays_from(*rays, first);
     const FuseOne* dd = (const FuseOne*)(ws + h.o_dets);
-    const size_t lds_tiles = fuse_tiles_lds(f.K, 1, small_k ? 2 : 1, true);
     if (linebuf)
-        hipLaunchKernelGGL(fuse_tiles_lb_kernel<true>, dim3(n_wg), dim3(OT_LB_BR), fuse_lb_lds(f.K), st, part, (uint32_t)count, dd, f.K,
-                           (uint32_t)piece);
+        hipLaunchKernelGGL(fuse_tiles_lb_kernel<true>, dim3(tp.n_wg), dim3(OT_LB_BR), fuse_lb_lds(f.K), st, part, (uint32_t)count, dd, f.K,
+                           (uint32_t)tp.piece);
     else if (small_k)
-        hipLaunchKernelGGL((fuse_tiles_kernel<false, 1, 2, true>), dim3(n_wg), dim3(OT_FUSE_BR), lds_tiles, st, part, (uint32_t)count,
-                           dd, 1, f.K, (uint32_t)piece);
+        hipLaunchKernelGGL((fuse_tiles_kernel<1, 2, true>), dim3(tp.n_wg), dim3(OT_FUSE_BR), fuse_tiles_lds(f.K), st, part, (uint32_t)count,
+                           dd, 1, f.K, (uint32_t)tp.piece);
     else
-        hipLaunchKernelGGL((fuse_tiles_kernel<false, 1, 1, true>), dim3(n_wg), dim3(OT_FUSE_BR), lds_tiles, st, part, (uint32_t)count,
-                           dd, 1, f.K, (uint32_t)piece);
+        hipLaunchKernelGGL((fuse_tiles_kernel<1, 1, true>), dim3(tp.n_wg), dim3(OT_FUSE_BR), fuse_tiles_lds(f.K), st, part, (uint32_t)count,
+                           dd, 1, f.K, (uint32_t)tp.piece);
     hipLaunchKernelGGL(spec_result_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)f.g.ext_slots,
                        (const unsigned int*)f.g.esc_n, f.g.esc_cap, result6);
     HIP_TRY(hipGetLastError());
@@ -2190,39 +2220,18 @@ extern "C" int ot_detector_image_auto_finish(ot_auto_image* im_raw, const double
     hipStream_t st = (hipStream_t)stream;
     if (st != im->st) return fail(OT_ERR_INVALID, "ot_detector_image_auto_finish: not the stream of ot_detector_image_auto_begin");
     // (the scratch block of begin is still ours: the handle holds its lease)
-    const double* table = observer_table_device();
-    if (!table) return fail(OT_ERR_HIP, "could not upload the CIE observer table");
+    const double* table = nullptr;
+    if (int rc = detector_setup(&table)) return rc;
     FuseOne& f = im->f;
-    f.a.x0 = extent[0];
-    f.a.x1 = extent[1];
-    f.a.y0 = extent[2];
-    f.a.y1 = extent[3];
-    f.a.fx = (double)Nx / (extent[1] - extent[0]);  // Nx / s[0]  misc.py:75
-    f.a.fy = (double)Ny / (extent[3] - extent[2]);
-    f.a.Nx = Nx;
-    f.a.Ny = Ny;
-    f.a.ws = 1.0;
+    f.a = render_args(extent, Nx, Ny, 1.0);
     f.hist = hist;
-    char* ws = im->ws;
-    FuseIndex ix;
-    ix.tile_n = (unsigned int*)(ws + im->o_tn);
-    ix.tstart = (unsigned int*)(ws + im->o_ts);
-    ix.wstart = (unsigned int*)(ws + im->o_ws);
-    ix.n_slabs = im->n_slabs;
-    ix.list = (unsigned int*)(ws + im->o_list);
-    ix.slabs = (double*)(ws + im->o_slabs);
-    const int lds_accum = (OT_TILE_PX * 4 + OT_OBS_N * 6) * (int)sizeof(double);  // tile + (value, difference) observer table
-    static thread_local bool lds_set[64] = {false};
-    if (im->dev >= 0 && im->dev < 64 && !lds_set[im->dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)spec_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_accum));
-        lds_set[im->dev] = true;
-    }
+    const FuseIndex ix = im->idx.at(im->ws, 0);
     HIP_TRY(hipMemsetAsync(ix.tile_n, 0, sizeof(unsigned int) * f.K, st));
     const unsigned gc = (f.cap + 1024 * OT_FUSE_IDX_PER - 1) / (1024 * OT_FUSE_IDX_PER);
     hipLaunchKernelGGL(fuse_chunk_hist_kernel, dim3(gc), dim3(1024), 0, st, f, ix);
     hipLaunchKernelGGL(fuse_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, f, ix);
     hipLaunchKernelGGL(fuse_chunk_place_kernel, dim3(gc), dim3(1024), 0, st, f, ix);
-    hipLaunchKernelGGL(spec_accum_kernel, dim3(std::min<unsigned>(ix.n_slabs, (unsigned)cu_count())), dim3(1024), lds_accum, st, f, ix, table);
+    hipLaunchKernelGGL(spec_accum_kernel, dim3(std::min<unsigned>(ix.n_slabs, (unsigned)cu_count())), dim3(1024), OT_ACCUM_LDS, st, f, ix, table);
     hipLaunchKernelGGL(spec_reduce_kernel, dim3(OT_TILE_PX / 256, (unsigned)f.K), dim3(256), 0, st, f, ix);
     hipLaunchKernelGGL(spec_escaped_kernel, dim3(64), dim3(256), 0, st, f, table);
     HIP_TRY(hipGetLastError());
@@ -2294,14 +2303,6 @@ extern "C" int ot_image_convolve(const double* in, int32_t Nx, int32_t Ny, const
 }
 
 // ---- spectrum rendering ---------------------------------------------------------------------------------------
-static int cu_count() {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        return prop.multiProcessorCount;
-    return 256;
-}
-
 static int spectrum_range(int64_t n, const unsigned int* fill, const float* wl, const float* w, double* range2, int64_t* count,
                           void* stream);
 static int spectrum_histogram(int64_t n, const unsigned int* fill, const float* wl, const float* w, const float* edges,

@@ -3,7 +3,6 @@
 // spherical_surface.py:36-97, RenderImage.render render_image.py:361-421 (+ misc.binning_indices_2d
 // misc.py:59-91, color.x/y/z_observer observers.py:14-41).
 #pragma once
-#include <vector>
 #include "ot_device.hpp"
 #include "cie_observer_table.inc"
 
@@ -527,29 +526,6 @@ struct RenderArgs {
     double ws;      // every hit's weight times this, in f64, before it is added (1: plain; iterative_render: rays_step / N)
 };
 
-static const double* observer_table_device() {
-    static thread_local const double* tab[64] = {nullptr};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    if (!tab[dev]) {
-        // the 471 x 3 table, and behind it the same as (value, difference to the next row) pairs: 471 x 6 (observer_xyz_at6)
-        std::vector<double> both((size_t)OT_OBS_N * 9);
-        const double* src = (const double*)ot_observer_xyz;
-        for (int i = 0; i < OT_OBS_N * 3; i++) both[i] = src[i];
-        double* pairs = both.data() + (size_t)OT_OBS_N * 3;
-        for (int j = 0; j < OT_OBS_N; j++)
-            for (int c = 0; c < 3; c++) {
-                pairs[6 * j + 2 * c] = src[3 * j + c];
-                pairs[6 * j + 2 * c + 1] = (j + 1 < OT_OBS_N) ? (src[3 * (j + 1) + c] - src[3 * j + c]) / 1.0 : 0.0;  // observers.py:14-41
-            }
-        double* d = nullptr;
-        if (hipMalloc((void**)&d, sizeof(double) * both.size()) != hipSuccess) return nullptr;
-        if (hipMemcpy(d, both.data(), sizeof(double) * both.size(), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        tab[dev] = d;
-    }
-    return tab[dev];
-}
-
 // RenderImage.render render_image.py:396-418.
 //   * the 471x3 CIE observer table (11 KB) is staged in LDS once per workgroup: every lane indexes it with its
 //     own wavelength;
@@ -594,7 +570,7 @@ OT_DEV void observer_xyz_at(const double* obs, double l, double& xo, double& yo,
     }
 }
 
-// The same from the table of (value, difference) pairs (observer_table_device: 471 x 6 behind the 471 x 3), for the kernels
+// The same from the table of (value, difference) pairs (detector_setup in ot_api.hip: 471 x 6 behind the 471 x 3), for the kernels
 // that look a wavelength up per RECORD out of LDS: the three pairs of a row are 48 contiguous, 16-byte aligned bytes -- three
 // 16-byte LDS reads instead of six 8-byte ones with a 24-byte row stride -- and the difference np.interp forms per call
 // ((f[j + 1] - f[j]) / 1.0, the same f64 subtraction) comes ready: identical bits.

@@ -92,7 +92,6 @@ OT_DEV int fuse_pixel(FT& F, const V3& ph, int32_t& ix, int32_t& iy) {
 // of a detector writes the verdict.  (One 1024-thread workgroup per detector walking its 4096 samples in four rounds on a
 // single CU took 70 us in front of every image.)
 #define OT_FUSE_PROBE_WG 256
-template <bool NUMERIC>
 __global__ __launch_bounds__(OT_FUSE_PROBE_WG) void fuse_probe_kernel(ot_rays R, int64_t first, int64_t count,
                                                                       const FuseOne* __restrict__ dets, int* __restrict__ pset_all,
                                                                       int* __restrict__ pcnt_all) {
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(OT_FUSE_PROBE_WG) void fuse_probe_kernel(ot_rays R,
     V3 ph;
     float w;
     bool valid, ill, to;
-    detector_hit<NUMERIC>(R, r, in_sample, F, sp, pair_direction(sp), ph, w, valid, ill, to);
+    detector_hit<false>(R, r, in_sample, F, sp, pair_direction(sp), ph, w, valid, ill, to);
     int32_t ix, iy;
     const int pix = valid ? fuse_pixel(F, ph, ix, iy) : -1;
     bool is_new = false;
@@ -136,22 +135,11 @@ __global__ __launch_bounds__(OT_FUSE_PROBE_WG) void fuse_probe_kernel(ot_rays R,
     }
 }
 
-// wave-aggregated report of the numeric hit search
-template <class FT>
-OT_DEV void fuse_count_ill(FT& F, bool any_ill, bool timeout) {
-    const unsigned long long m_ill = __ballot(any_ill), m_to = __ballot(timeout);
-    if (__lane_id() == 0) {
-        if (m_ill) atomicAdd(&F.ill[0], (unsigned long long)__popcll(m_ill));
-        if (m_to) atomicAdd(&F.ill[1], (unsigned long long)__popcll(m_to));
-    }
-}
-
 // ---- direct path: detectors whose hits fall into few pixels -------------------------------------------------
 // render_kernel (ot_detector.hpp) with the hit search in front; the LDS hash is shared by the detectors of the launch
-// (key = pixel * 8 + detector).
-// GENERAL = false: flat / conic detectors without a sphere projection (the usual case) -- a kernel without the Illinois
-// loop, the spline code and the projection polynomials.
-template <bool GENERAL, int NDET>
+// (key = pixel * 8 + detector).  Flat / conic detectors without a sphere projection only (fused_ok in ot_api.hip): no
+// Illinois loop, no spline code, no projection polynomials.
+template <int NDET>
 __global__ __launch_bounds__(1024) void fuse_direct_kernel(ot_rays R, int64_t first, int64_t count,
                                                            const FuseOne* __restrict__ dets, int n_det,
                                                            const double* __restrict__ table) {
@@ -200,12 +188,10 @@ __global__ __launch_bounds__(1024) void fuse_direct_kernel(ot_rays R, int64_t fi
             bool valid = false, ill = false, to = false;
             // flat detector behind the last surface (the usual case): settled from the prefetched pair; the section search
             // only if a lane of the wave needs it
-            bool settled = false;
-            if (!GENERAL) settled = detector_hit_last(F, R.nt, active, sp, sdir, ph, w, valid);
-            if (GENERAL || __ballot(!settled) != 0ull) {
-                if (!settled) detector_hit<GENERAL, GENERAL>(R, r, active, F, sp, sdir, ph, w, valid, ill, to);
+            const bool settled = detector_hit_last(F, R.nt, active, sp, sdir, ph, w, valid);
+            if (__ballot(!settled) != 0ull) {
+                if (!settled) detector_hit<false, false>(R, r, active, F, sp, sdir, ph, w, valid, ill, to);
             }
-            if (GENERAL) fuse_count_ill(F, ill, to);
             int32_t ix, iy;
             const int pix = valid ? fuse_pixel(F, ph, ix, iy) : -1;
             valid = valid && pix >= 0;
@@ -299,17 +285,9 @@ OT_DEV void spec_extent_flush(unsigned long long* slots, const double ext[4]) {
 
 // RPT rays per thread and sub-block (2 where the detectors' images have at most 1024 tiles: more loads in flight per
 // barrier); R's pointers are advanced to the first ray of the range by the host, rays are addressed with 32 bits.
-// LDS of the tile kernel: 6 KT + 10 counters, then (one detector) the staging area of a sub-block's records
-__host__ __device__ static inline size_t fuse_stage_offset(int KT) {
-    return (sizeof(unsigned int) * (6 * (size_t)KT + OT_DET_MAX + 2) + 15) / 16 * 16;
-}
-__host__ __device__ static inline size_t fuse_tiles_lds(int KT, int n_det, int rpt, bool specx) {
-    const size_t counters = sizeof(unsigned int) * (5 * (size_t)(KT > 1 ? KT : 1) + OT_DET_MAX);
-#ifndef OT_FUSE_SORT
-    return counters;
-#endif
-    if (n_det != 1) return counters;
-    return fuse_stage_offset(KT) + (size_t)OT_FUSE_BR * rpt * (specx ? 28 : 16);
+// LDS of the tile kernel: 5 KT + 8 counters
+__host__ __device__ static inline size_t fuse_tiles_lds(int KT) {
+    return sizeof(unsigned int) * (5 * (size_t)(KT > 1 ? KT : 1) + OT_DET_MAX);
 }
 
 // SPECX: the speculative-grid form (one detector, closed-form hit): the tile comes from SpecGrid instead of the image's
@@ -317,7 +295,7 @@ __host__ __device__ static inline size_t fuse_tiles_lds(int KT, int n_det, int r
 // PAIR: the storage has two sections (tail storage): detector_hit_pair settles every ray from the prefetched pair, the
 // section search is not compiled in (with eight detectors unrolled it was most of the kernel: 11 700 instructions, 157 scalar
 // registers spilled into vector lanes).
-template <bool GENERAL, int NDET, int RPT, bool SPECX = false, bool PAIR = false>
+template <int NDET, int RPT, bool SPECX = false, bool PAIR = false>
 __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint32_t count, const FuseOne* __restrict__ dets,
                                                                 int n_det, int KT, uint32_t piece) {
     // the probe's verdicts, read ONCE: a load of spread[0] inside the loop below is a vector-memory operation like the
@@ -329,34 +307,15 @@ __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint3
     if (!spread_mask) return;
     constexpr uint32_t BRT = OT_FUSE_BR * RPT;        // rays per sub-block
     constexpr int TB = (RPT == 1) ? 11 : 10;          // bits of the tile number in a record key
-    // SORT (one detector, -DOT_FUSE_SORT): the records of a sub-block are gathered tile by tile in LDS before they are stored,
-    // so that neighbouring lanes write neighbouring records of one chunk instead of 64 different chunks per store
-    // instruction.  Built because the record stores cost as much as everything else in this kernel together (C5, 9.3e7
-    // records of 24 B: 2.10 ms; 1.05 ms without the stores, 1.62 ms with the same stores aimed at 400 KB per workgroup);
-    // measured: no gain (C5 image 3.17 = 3.17 ms, C4 with a known extent 3.4 against 3.2 ms) -- a tile receives ~3 records
-    // per sub-block, the runs stay shorter than a cache line.  Off by default.
-#ifdef OT_FUSE_SORT
-    constexpr bool SORT = (NDET == 1);
-#else
-    constexpr bool SORT = false;
-#endif
+    // (Not kept: gathering a sub-block's records tile by tile in LDS before the stores, so that neighbouring lanes write
+    // neighbouring records -- no gain, C5 image 3.17 = 3.17 ms: a tile receives ~3 records per sub-block.)
     extern __shared__ unsigned int fl[];
     unsigned int* cnt = fl;  // [2][KT]
     unsigned int* fill = fl + 2 * KT;
     unsigned int* cur = fl + 3 * KT;
     unsigned int* nb = fl + 4 * KT;
     unsigned int* next = fl + 5 * KT;  // [n_det] next free chunk of this workgroup's part of each detector's pool
-    unsigned int* sbase = next + OT_DET_MAX;  // SORT [KT]: first staging slot of a tile's records of this sub-block
-    unsigned int* stop = sbase + KT;          // SORT [2]: staging slots taken (by sub-block parity)
-    char* stg = (char*)fl + fuse_stage_offset(KT);
-    double* sx = (double*)stg;                // SPECX: [BRT] x, [BRT] y
-    double* sy = sx + BRT;
-    float* sw = (float*)(SPECX ? stg + 16 * BRT : stg);  // [BRT] weight, [BRT] wavelength
-    float* swl = sw + BRT;
-    unsigned int* sdst = (unsigned int*)(swl + BRT);     // [BRT] record number in the pool, OT_FUSE_NONE: dropped
-    unsigned int* spx = sdst + BRT;                      // plain records: [BRT] pixel in the tile
     if (threadIdx.x < (unsigned)n_det) next[threadIdx.x] = blockIdx.x * as_const(dets)[threadIdx.x].per_wg;
-    if (SORT && threadIdx.x < 2) stop[threadIdx.x] = 0u;
     for (int e = threadIdx.x; e < KT; e += blockDim.x) {
         cnt[e] = 0u;
         cnt[KT + e] = 0u;
@@ -424,17 +383,15 @@ __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint3
                 V3 ph;
                 float w;
                 bool valid = false, ill = false, to = false;
-                // flat detector behind the last surface (the usual case): no section search; the wave takes the general
-                // path only if one of its lanes needs it
+                // flat detector behind the last surface (the usual case): no section search; the wave searches the sections
+                // only if one of its lanes needs it
                 if constexpr (PAIR) {
                     detector_hit_pair(F, act[j], sp[j], sdir, ph, w, valid);
                 } else {
-                    bool settled = false;
-                    if (!GENERAL) settled = detector_hit_last(F, R.nt, act[j], sp[j], sdir, ph, w, valid);
-                    if (GENERAL || __ballot(!settled) != 0ull) {
-                        if (!settled) detector_hit<GENERAL, GENERAL>(R, r, act[j], F, sp[j], sdir, ph, w, valid, ill, to);
+                    const bool settled = detector_hit_last(F, R.nt, act[j], sp[j], sdir, ph, w, valid);
+                    if (__ballot(!settled) != 0ull) {
+                        if (!settled) detector_hit<false, false>(R, r, act[j], F, sp[j], sdir, ph, w, valid, ill, to);
                     }
-                    if (GENERAL) fuse_count_ill(F, ill, to);
                 }
                 if (!valid) continue;
                 unsigned int local, tile;
@@ -465,7 +422,6 @@ __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint3
         fuse_lds_barrier();
         // phase 2: the previous sub-block's counts move the open chunks on; tiles whose open chunk overflows with this
         // sub-block's records take new chunks from the workgroup's part of their detector's pool
-        if (SORT && threadIdx.x == 0) stop[par ^ 1] = 0u;  // (last read before this round's first barrier)
         for (int e = threadIdx.x; e < KT; e += blockDim.x) {
             const unsigned int cb = cnt_b[e];
             if (cb) {
@@ -474,7 +430,6 @@ __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint3
             }
             const unsigned int c = cnt_a[e];
             if (!c) continue;
-            if (SORT) sbase[e] = atomicAdd(&stop[par], c);  // the tile's records stand together, tiles in any order
             const unsigned int f = fill[e] + c;
             if (f <= OT_FUSE_CH) continue;
             int d = 0;
@@ -495,7 +450,7 @@ __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint3
         }
         fuse_lds_barrier();
         // phase 3: one 12-byte store per hit.  (The next phase 2 changes fill / cur / nb only behind the next barrier,
-        // which every wave reaches after these reads.)  SORT: into the staging slots first.
+        // which every wave reaches after these reads.)
 #pragma unroll
         for (int j = 0; j < RPT; j++) {
 #pragma unroll
@@ -514,18 +469,7 @@ __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint3
                     chunk = nb[e] + dest / OT_FUSE_CH;
                     dest %= OT_FUSE_CH;
                 }
-                if constexpr (SORT) {
-                    const unsigned int t = sbase[e] + rank;
-                    sdst[t] = (chunk < F.cap) ? chunk * OT_FUSE_CH + dest : OT_FUSE_NONE;  // (pool < 2^32 records: host)
-                    sw[t] = wk[j][d];
-                    swl[t] = wl[j];
-                    if constexpr (SPECX) {
-                        sx[t] = hx[j];
-                        sy[t] = hy[j];
-                    } else {
-                        spx[t] = local;
-                    }
-                } else if (chunk < F.cap) {
+                if (chunk < F.cap) {  // (pool < 2^32 records: host)
                     if constexpr (SPECX) {
                         SpecRec* dst = (SpecRec*)F.rec + ((size_t)chunk * OT_FUSE_CH + dest);
                         SpecRec rec = {hx[j], hy[j], wk[j][d], wl[j]};
@@ -534,24 +478,6 @@ __global__ __launch_bounds__(OT_FUSE_BR) void fuse_tiles_kernel(ot_rays R, uint3
                         TileRec rec = {wk[j][d], wl[j], local};
                         F.rec[(size_t)chunk * OT_FUSE_CH + dest] = rec;
                     }
-                }
-            }
-        }
-        if constexpr (SORT) {
-            // phase 4: the staged records in slot order -- lanes next to each other write records next to each other
-            fuse_lds_barrier();
-            const auto& F = as_const(dl)[0];
-            const unsigned int n_rec = stop[par];
-            for (unsigned int t = threadIdx.x; t < n_rec; t += OT_FUSE_BR) {
-                unsigned int dsti = sdst[t];
-                if (dsti == OT_FUSE_NONE) continue;
-
-                if constexpr (SPECX) {
-                    SpecRec rec = {sx[t], sy[t], sw[t], swl[t]};
-                    ((SpecRec*)F.rec)[dsti] = rec;
-                } else {
-                    TileRec rec = {sw[t], swl[t], spx[t]};
-                    F.rec[dsti] = rec;
                 }
             }
         }
@@ -1021,9 +947,6 @@ OT_DEV void fuse_accum_body(const FuseOne& F, const FuseIndex& ix, const double*
         __syncthreads();  // the slab is out: the tile part holds wstart again in the next round
     }
 }
-__global__ __launch_bounds__(1024) void fuse_accum_kernel(FuseOne F, FuseIndex ix, const double* __restrict__ table) {
-    fuse_accum_body(F, ix, table, blockIdx.x, gridDim.x);
-}
 // several detectors in one launch (blockIdx.z), their records in device memory
 __global__ __launch_bounds__(1024) void fuse_accum_multi_kernel(const FuseOne* __restrict__ dets, const FuseIndex* __restrict__ ixs, const double* __restrict__ table) {
     fuse_accum_body(dets[blockIdx.z], ixs[blockIdx.z], table, blockIdx.x, gridDim.x);
@@ -1053,9 +976,6 @@ OT_DEV void fuse_reduce_body(const FuseOne& F, const FuseIndex& ix, const unsign
     hg[1] += s1;
     hg[2] += s2;
     hg[3] += s3;
-}
-__global__ __launch_bounds__(256) void fuse_reduce_kernel(FuseOne F, FuseIndex ix) {
-    fuse_reduce_body(F, ix, blockIdx.x, blockIdx.y);
 }
 // several detectors in one launch (blockIdx.z), their records in device memory
 __global__ __launch_bounds__(256) void fuse_reduce_multi_kernel(const FuseOne* __restrict__ dets, const FuseIndex* __restrict__ ixs) {
@@ -1129,7 +1049,7 @@ __global__ __launch_bounds__(64) void spec_result_kernel(const unsigned long lon
     if (k == 5 && esc_n) out[5] = (double)esc_cap;  // (on the device: result6 may be device memory)
 }
 
-// fuse_accum_kernel for SpecRec chunks: LDS window of tile t = final pixels [ox, ox + 64) x [oy, oy + 64)
+// fuse_accum_body for SpecRec chunks: LDS window of tile t = final pixels [ox, ox + 64) x [oy, oy + 64)
 __global__ __launch_bounds__(1024) void spec_accum_kernel(FuseOne F, FuseIndex ix, const double* __restrict__ table) {
     extern __shared__ double lds[];  // [TILE_PX * 4 window] [471 * 6 observer table: (value, difference) pairs]; the window part first holds wstart
     double* tile = lds;
@@ -1165,7 +1085,7 @@ __global__ __launch_bounds__(1024) void spec_accum_kernel(FuseOne F, FuseIndex i
         spec_origin(F, t, ox, oy);
         const SpecRec* __restrict__ recs = (const SpecRec*)F.rec;
         constexpr int PER = 1024 / OT_FUSE_CH;
-        constexpr int DEPTH = 4;  // two stages of DEPTH records in flight per thread, see fuse_accum_kernel
+        constexpr int DEPTH = 4;  // two stages of DEPTH records in flight per thread, see fuse_accum_body
         const int g = threadIdx.x / OT_FUSE_CH, slot = threadIdx.x % OT_FUSE_CH;
         const int n_c = (int)(j_end - j_begin);
         auto load = [&](int first, SpecRec* rec, bool* ok) {
@@ -1188,7 +1108,7 @@ __global__ __launch_bounds__(1024) void spec_accum_kernel(FuseOne F, FuseIndex i
                 observer_xyz_at6(obs, (double)rec[k].wl, xo, yo, zo);
                 const int lx = px - ox, ly = py - oy;
                 if ((unsigned)lx < (unsigned)OT_TILE_W && (unsigned)ly < (unsigned)OT_TILE_W) {
-                    double* hv = tile + ((ly << 6) | lx);  // plane-major window, see fuse_accum_kernel
+                    double* hv = tile + ((ly << 6) | lx);  // plane-major window, see fuse_accum_body
                     unsafeAtomicAdd(hv + 0 * OT_TILE_PX, xo * wm);
                     unsafeAtomicAdd(hv + 1 * OT_TILE_PX, yo * wm);
                     unsafeAtomicAdd(hv + 2 * OT_TILE_PX, zo * wm);

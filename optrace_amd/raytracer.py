@@ -6,7 +6,9 @@ Mirror of optrace/tracer/raytracer.py:28-1279 for the hot path named in BASELINE
 happens in HIP kernels reached through the C-ABI (include/optrace_amd.h):
 
     trace(N)          -> ot_generate_and_trace   (one fused launch: generation + every surface)
-    detector_image()  -> ot_detector_hits + ot_render_accumulate
+    detector_image()  -> ot_detector_images      (known extent: hit search and binning in one pass)
+                         ot_detector_image_auto_begin / _finish  (automatic extent, long bundles: one pass)
+                         ot_detector_hits_multi + ot_render_accumulate  (otherwise: hit list, then binning)
 
 Geometry validation (element order, collisions) is one-off host work per trace and stays in NumPy.
 """
@@ -702,8 +704,8 @@ class Raytracer(Group):
         spec = dict(detector_index=detector_index, source_index=source_index, extent=extent,
                     projection_method=projection_method)
         # extent known: one pass, no hit positions in memory -- except for long bundles on a spherical detector whose
-        # projection has a transcendental (the fused kernels would take their general form, numeric hit search included:
-        # the chain over a compact list of the hits inside the extent is faster, C3 1.55 -> 1.4 ms)
+        # projection has a transcendental (`ot_detector_images` would send that request through the chain with a dense hit
+        # list; the chain over a compact list of the hits inside the extent is faster, C3 1.55 -> 1.4 ms)
         projected = (0 <= detector_index < len(self.detectors) and self.rays.N >= self.COMPACT_HITS_FROM
                      and isinstance(self.detectors[detector_index].surface, SphericalSurface)
                      and projection_method in ("Equidistant", "Equal-Area", "Stereographic"))

@@ -112,8 +112,8 @@ def test_fused_spherical_detector_projections(projection):
 
 
 def test_fused_numeric_detector_and_no_hits():
-    """A tilted (numerically intersected) detector goes through the NUMERIC kernels; an extent without hits gives an
-    empty image instead of an error."""
+    """A tilted (numerically intersected) detector: `ot_detector_images` sends it through the chain (numeric hit search,
+    then binning), the same image as `_unfused`; an extent without hits gives an empty image instead of an error."""
     with ot.global_options.no_warnings():
         RT = ot.Raytracer(outline=[-10, 10, -10, 10, -10, 40], seed=11)
         RT.add(ot.RaySource(ot.RectangularSurface(dim=[2, 1]), divergence="Isotropic", div_angle=8, pos=[0, 0, 0]))

@@ -4,7 +4,7 @@
 `detector_image` picks at that size: the dense hit-list chain for automatic extents, `fuse_direct` for user extents.  The
 configurations of BASELINE.json (1e7 .. 2e8 rays) and `iterative_render` execute other kernels: compact hit lists, the
 one-pass speculative grid (`_auto_image_one_pass`), the tile kernels with and without line buffers, the multi-detector tile
-pass `fuse_tiles_kernel<false, 2 / 4 / 8, 1>`.  Here every one of them is forced onto the same fixtures (thresholds set to
+pass `fuse_tiles_kernel<2 / 4 / 8, 1>`.  Here every one of them is forced onto the same fixtures (thresholds set to
 1, `OT_RENDER_PATH`, `OT_TILE_LINEBUF`) and held to the same bar against the reference's own images
 (`det*/<projection>/img`, `det*/user/img` of tests/golden/trace_*.npz): extent 1e-9, power 1e-6, image norm 1e-4
 (BASELINE.json north_star).  Where a path does not apply to a fixture (point-like image, sphere projection) the test
@@ -144,7 +144,7 @@ def test_fused_user_extent_against_reference_images(name, path, linebuf):
 @pytest.mark.parametrize("K", [2, 3, 6])
 @pytest.mark.parametrize("name", NAMES)
 def test_multi_detector_tile_pass_against_reference_images(name, K):
-    """The kernel `iterative_render` and the sharded forms run -- `fuse_tiles_kernel<false, 2 | 4 | 8, 1>`, K images per pass
+    """The kernel `iterative_render` and the sharded forms run -- `fuse_tiles_kernel<2 | 4 | 8, 1>`, K images per pass
     over the sections, then the `*_multi_kernel` second pass -- with automatic extents from the extent-only pass
     (`_auto_extents`): K copies of every (detector, projection) request in one call, each against the reference's image."""
     g, RT = gpu_trace(name)
