@@ -37,15 +37,14 @@ def check_in(key: str, val, choices) -> None:
 
 
 _EPOCH = [0]
-_SAW_WRITEABLE = [False]  # set by crepr when it meets a large array that can still be edited in place
-_WATCH = [None]           # [list or None]: while a list, crepr adds the small arrays it meets that can still be edited in
-                          # place (RaySource.s, conv_pos, the outline); Raytracer.trace collects them for its shortcut
+SMALL_ARRAY = 20  #: arrays with fewer elements go into `crepr` by value
 
 
 def mutation_epoch() -> int:
     """Counts attribute assignments on tracked objects (everything a trace depends on is a BaseClass whose arrays
     are read-only and whose state changes only through `__setattr__`).  While it stands still, nothing a
-    Raytracer compiled or checked can have changed, so `Raytracer.trace` may skip its snapshot comparison."""
+    Raytracer compiled or checked can have changed, so `Raytracer.trace` may skip its snapshot comparison.  Nothing
+    rewinds it: state that no trace depends on (detectors and their own surfaces) is untracked instead."""
     return _EPOCH[0]
 
 
@@ -59,8 +58,6 @@ def _array_token(a: np.ndarray) -> tuple:
     alone is reused once the old array is freed and says nothing about in-place edits, so the token also carries the
     shape and a content checksum: of everything while the array is writeable, of 64 evenly spread elements once it is
     locked read-only (its content cannot change any more, the samples only tell a recycled id apart)."""
-    if a.flags.writeable:
-        _SAW_WRITEABLE[0] = True
     flat = a.reshape(-1) if a.flags.c_contiguous else a.ravel()
     part = flat if a.flags.writeable else flat[::max(1, flat.shape[0] // 64)]
     return id(a), a.shape, zlib.crc32(np.ascontiguousarray(part).view(np.uint8)) if part.dtype != object else 0
@@ -69,7 +66,7 @@ def _array_token(a: np.ndarray) -> tuple:
 class BaseClass:
     """Description strings, copy, read-only locking and a compact state representation."""
 
-    _tracked = True  #: False for result containers (ray storage, images): their attributes never feed a trace
+    _tracked = True  #: False where attributes never feed a trace: result containers (ray storage, images), detectors
 
     def __init__(self, desc: str = "", long_desc: str = "") -> None:
         self._lock = False
@@ -77,18 +74,18 @@ class BaseClass:
         self.desc = desc
         self.long_desc = long_desc
 
-    def crepr(self) -> list:
+    def crepr(self, writeable: list = None) -> list:
         """State as nested lists / tuples of plain values; compared to detect changes since the last trace
-        (base_class.py:27-58).  Small arrays go in by value, large ones as a token (`_array_token`), callables by id."""
+        (base_class.py:27-58).  Small arrays go in by value, large ones as a token (`_array_token`), callables by id.
+        `writeable`: a list that collects the arrays met that can still be edited in place (RaySource.s, conv_pos, ...:
+        the reference re-reads them at every trace)."""
         def plain(v):
             if isinstance(v, BaseClass):
-                return v.crepr()
+                return v.crepr(writeable)
             if isinstance(v, np.ndarray):
-                if v.size >= 20:
-                    return _array_token(v)
-                if v.flags.writeable and _WATCH[0] is not None:  # the reference re-reads such arrays at every trace
-                    _WATCH[0].append(v)
-                return tuple(v.ravel().tolist())
+                if v.flags.writeable and writeable is not None:
+                    writeable.append(v)
+                return _array_token(v) if v.size >= SMALL_ARRAY else tuple(v.ravel().tolist())
             if isinstance(v, list):
                 return tuple(v)
             return id(v) if callable(v) else v

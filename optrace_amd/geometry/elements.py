@@ -134,6 +134,8 @@ class Element(BaseClass):
         if key in ("front", "back") and val is not None:
             check_type(key, val, (Surface, Point, Line) if self._allow_non_2D else Surface)
             val = val.copy()  # elements own private copies of their surfaces (element.py:223-231)
+            # ... tracked like the element: a detector's surface feeds no trace (base.mutation_epoch)
+            val.__dict__["_tracked"] = self._tracked
         elif key in ("d1", "d2") and val is not None:
             check_type(key, val, (int, float))
             val = float(val)
@@ -248,6 +250,7 @@ class Detector(_SingleSurface):
     """Surface on which images are rendered (detector.py:11-43)."""
 
     abbr = "DET"
+    _tracked = False  # nothing a trace depends on: moving it (iterative_render does, position by position) is no scene change
 
     def __setattr__(self, key, val):
         if key == "front":

@@ -137,21 +137,20 @@ class RayStorage(BaseClass):
         self._dev = {}    # name -> torch tensor (flat, component-major)
         self._host = {}   # name -> cached read-only numpy view
         self._powers = []
-        self._ranges = None   # ot_source_range array of the current split
-        self._split_key = None
+        self._ranges = None   # ot_source_range array of the current split (`_source_ranges`)
         self._rays_c = None   # ot_rays of the current buffers
         super().__init__(**kwargs)
 
     # ---- allocation (ray_storage.py:35-90) ---------------------------------------------------------
     def init(self, ray_source_list: list, N: int, nt: int, no_pol: bool, _single_power: float = None,
-             _N_list=None, _rng=None, _power_scale: float = 1.0, _split=None, _keep_ranges: bool = False,
+             _N_list=None, _rng=None, _power_scale: float = 1.0, _split=None, _ranges=None,
              _alloc: bool = True) -> None:
         """`_alloc=False`: the split, the ranges and the source powers only, no section buffers (the book-keeping of a
         render-only trace, `TailStorage`).
         `_power_scale`: the share of the sources' power this storage carries (one rank's shard of a sharded trace);
-        `_split`: (N_list, dN, p) precomputed by `split_rays` for exactly these sources and N; `_keep_ranges`: the
-        caller knows the sources did not change since the previous init (the range records are reused if the split is
-        the same deterministic one)."""
+        `_split`: (N_list, dN, p) precomputed by `split_rays` for exactly these sources and N; `_ranges`: the range
+        records of exactly this split, powers and power scale (`_source_ranges` of an earlier init), None: computed when
+        first needed."""
         d = self.__dict__  # plain dict writes: this runs once per trace
         d["_lock"] = False
         d["no_pol"] = no_pol
@@ -175,10 +174,7 @@ class RayStorage(BaseClass):
         d["B_list"] = np.concatenate(([0], np.cumsum(N_list))).astype(int)
         d["ray_source_list"] = ray_source_list
         d["_powers"] = [float(_single_power or RS.power) * _power_scale for RS in ray_source_list]
-        split_key = (int(N), float(_power_scale), dN == 0 and _N_list is None and _single_power is None)
-        if not (_keep_ranges and split_key[2] and split_key == self._split_key):
-            d["_ranges"] = None
-        d["_split_key"] = split_key
+        d["_ranges"] = _ranges
 
         N, nt = int(N), int(nt)
         if not _alloc:

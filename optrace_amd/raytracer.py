@@ -39,6 +39,18 @@ from . import detector as _detector
 from . import checks as _checks
 
 
+class _TraceRecord:
+    """What a full trace established, valid while `Raytracer._scene_unchanged()`.  The slow path of `trace` drops it as a
+    whole: no split, range record or book-keeping of render-only traces outlives a change of the scene."""
+    __slots__ = ("epoch", "structure", "snap", "scene", "watch", "splits", "ranges", "book")
+
+    def __init__(self, snap: dict, scene: CompiledScene, watch: list) -> None:
+        self.epoch = self.structure = None  # mutation_epoch(), Raytracer._structure(): read when its trace is done
+        self.snap, self.scene, self.watch = snap, scene, watch  # tracing_snapshot(), [(small writeable array, its bytes)]
+        self.splits, self.ranges = {}, {}  # N -> split_rays(); (N, power scale) -> range records of a split without remainder
+        self.book = None  # RayStorage without buffers: split, ranges and powers of render-only traces
+
+
 class Raytracer(Group):
 
     N_EPS: float = 1e-11
@@ -106,18 +118,17 @@ class Raytracer(Group):
         self._scene_key = None
         self._checked_key = None
         self._rays_known_current = False
-        self._source_cache = None  # (key, SourceTable): device copy of the source records, reused while unchanged
-        self._fast = None  # what the last full trace established, valid while base.mutation_epoch() stands still
+        self._source_cache = None  # (key, SourceTable, power scale): device copy of the source records, reused while unchanged
+        self._record = None        # _TraceRecord of the last full trace: the shortcut of `trace` for an unchanged scene
         self._msgs_host = None
         self._kernel_ms_log = None  # a list: every trace appends its kernel's duration (HIP events of the library; bench.py)
-        self._tail_book = None      # RayStorage without buffers: split, ranges and powers of render-only traces
         super().__init__(None, n0, **kwargs)
         self._new_lock = True
 
     # bookkeeping of the tracer itself: writing these is not a scene change (base.mutation_epoch)
     _INTERNAL = frozenset(("_msgs", "_last_trace_snapshot", "_scene", "_scene_handle", "_scene_key", "_checked_key",
-                           "_rays_known_current", "_source_cache", "geometry_error", "fault_pos", "_fast",
-                           "_msgs_host", "_kernel_ms_log", "_tail_book", "_lock", "_new_lock",
+                           "_rays_known_current", "_source_cache", "geometry_error", "fault_pos", "_record",
+                           "_msgs_host", "_kernel_ms_log", "_lock", "_new_lock",
                            "seed"))  # (the RNG seed is read at every trace and part of nothing that is compiled or checked)
 
     def __setattr__(self, key: str, val: Any) -> None:
@@ -153,14 +164,17 @@ class Raytracer(Group):
     # ---- change detection (raytracer.py:129-179) ------------------------------------------------------
     _SNAP_LISTS = (("Lenses", "lenses"), ("Filters", "filters"), ("Apertures", "apertures"), ("RaySources", "ray_sources"))
 
-    def tracing_snapshot(self) -> dict:
-        """State of everything a trace depends on, as nested lists / tuples of plain values (compared, not hashed)."""
+    def tracing_snapshot(self, writeable: list = None) -> dict:
+        """State of everything a trace depends on, as nested lists / tuples of plain values (compared, not hashed).
+        `writeable`: a list that collects the arrays met that can still be edited in place (`BaseClass.crepr`)."""
         rays = self.rays
+        if writeable is not None and self.outline.flags.writeable:
+            writeable.append(self.outline)
         snap = {"Rays": [rays.N, rays.Nt, rays.no_pol],
-                "Ambient": [tuple(self.outline), self.n0.crepr()],
+                "Ambient": [tuple(self.outline), self.n0.crepr(writeable)],
                 "TraceSettings": [self.no_pol, self.use_hurb, self.HURB_FACTOR]}
         for key, attr in self._SNAP_LISTS:
-            snap[key] = [el.crepr() for el in getattr(self, attr)]
+            snap[key] = [el.crepr(writeable) for el in getattr(self, attr)]
         return snap
 
     def property_snapshot(self) -> dict:
@@ -217,13 +231,12 @@ class Raytracer(Group):
                     + self._EVENT_TEXT[self.INFOS(kind).name].format(s=sec, n=where))
 
     # ---- geometry checks (raytracer.py:510-664) ---------------------------------------------------------
-    def _pretrace_check(self, N: int, snap: dict = None) -> bool:
+    def _pretrace_check(self, N: int, key: str) -> bool:
         check_type("N", N, int)
         if N < 1:
             raise ValueError(f"Ray number N needs to be at least 1, but is {N}.")
         # the checks sample every surface pair on a 100 x 100 grid (host NumPy); skip them while nothing that
-        # they depend on changed since they last passed (chunked rendering calls trace() many times)
-        key = self._geometry_key(snap)
+        # they depend on changed (`key`: `_geometry_key`) since they last passed (chunked rendering calls trace() many times)
         if self._checked_key is None or key != self._checked_key or self.geometry_error:
             self._geometry_checks()
             self._checked_key = key if not self.geometry_error else None
@@ -254,10 +267,9 @@ class Raytracer(Group):
         return _checks.collision_points(front, back, res)
 
     # ---- scene upload --------------------------------------------------------------------------------------
-    def _compile(self, snap: dict = None) -> CompiledScene:
-        """Flatten the scene and upload its tables; reused while the tracing-relevant state is unchanged."""
+    def _compile(self, key: str) -> CompiledScene:
+        """Flatten the scene and upload its tables; reused while `_geometry_key` is unchanged."""
         lib = _capi.load_library()
-        key = self._geometry_key(snap)
         if self._scene is not None and self._scene_handle is not None and key == self._scene_key:
             return self._scene
         self._release_scene()
@@ -303,9 +315,9 @@ class Raytracer(Group):
     def _scene_unchanged(self) -> bool:
         """Is everything the last full trace established (checks passed, compiled scene, source table) still valid?  One
         integer comparison, the identities of the list members and the bytes of the few small writeable arrays."""
-        fast = self._fast
-        return (fast is not None and fast[0] == _base.mutation_epoch() and fast[1] == self._structure()
-                and not self.geometry_error and all(a.tobytes() == b for a, b in fast[5]))
+        rec = self._record
+        return (rec is not None and rec.epoch == _base.mutation_epoch() and rec.structure == self._structure()
+                and not self.geometry_error and all(a.tobytes() == b for a, b in rec.watch))
 
     def trace(self, N: int, _initial_rays: tuple = None, _hurb_normals: np.ndarray = None, _N_list=None,
               _chunk: int = 0, _power_scale: float = 1.0, _tail: TailStorage = None, _tail_room: int = 0) -> None:
@@ -325,55 +337,52 @@ class Raytracer(Group):
         derived from it -- geometry checks, the compiled scene, the source table, the snapshot -- is kept while
         nothing changed: every tracked object reports assignments to a global counter (base.mutation_epoch), so
         an unchanged scene is recognised by one integer comparison, the identities of the list members and the bytes of
-        the few small arrays that are still writeable (large ones are read-only or switch the shortcut off).
+        the few small arrays that are still writeable (large ones are read-only or switch the shortcut off).  All but the
+        source table (`_source_cache`, keyed by content) is one `_TraceRecord`, replaced as a whole on a change.
         """
         if _tail is not None and _initial_rays is not None:
             raise ValueError("a render-only trace generates its rays on the device")
-        fast = self._fast
-        if self._scene_unchanged():
+        shortcut = self._scene_unchanged()
+        if shortcut:
             check_type("N", N, int)
             if N < 1:
                 raise ValueError(f"Ray number N needs to be at least 1, but is {N}.")
-            _, _, snap, scene, splits, _ = fast
-            snap = dict(snap)
-            writeable = False
+            rec, publish = self._record, False
         else:
-            self._fast = fast = None
-            _base._SAW_WRITEABLE[0] = False
-            _base._WATCH[0] = [self.outline] if self.outline.flags.writeable else []
-            snap = self.tracing_snapshot()  # taken once: geometry-check key, scene key and the post-trace record
-            writeable = _base._SAW_WRITEABLE[0]  # large arrays that can still change in place: no shortcut next time
-            # small arrays that can: their bytes are compared before every shortcut (assignments move the counter, an
-            # edit in place like `RT.outline[5] += 1` or `RS.s[0] = 0.1` does not)
-            watch = [(a, a.tobytes()) for a in _base._WATCH[0]]
-            _base._WATCH[0] = None
-            if self._pretrace_check(N, snap):
+            self._record = None
+            writeable = []
+            snap = self.tracing_snapshot(writeable)  # taken once: geometry key and the post-trace record
+            key = self._geometry_key(snap)
+            if self._pretrace_check(N, key):
                 return
-            scene = self._compile(snap)
-            splits = {}
+            # large arrays that can still change in place: no shortcut next time; small ones: their bytes are compared
+            # before every shortcut (assignments move the counter, an edit in place like `RS.s[0] = 0.1` does not)
+            publish = all(a.size < _base.SMALL_ARRAY for a in writeable)
+            rec = _TraceRecord(snap, self._compile(key), [(a, a.tobytes()) for a in writeable] if publish else [])
         lib = _capi.load_library()
         dev = require_device()
 
-        nt = scene.nt
+        nt = rec.scene.nt
         if _tail is None and self.rays.storage_size(N, nt, self.no_pol) > self.MAX_RAY_STORAGE_RAM:
             raise RuntimeError(f"More than {self.MAX_RAY_STORAGE_RAM*1e-9:.1f} GB RAM requested. Either decrease"
                                " the number of rays, surfaces or do an iterative render. If your system can handle"
                                " more RAM usage, increase the Raytracer.MAX_RAY_STORAGE_RAM parameter.")
 
-        split = splits.get(N)
+        split = rec.splits.get(N)
         if split is None:
-            split = splits[N] = RayStorage.split_rays(self.ray_sources, N)
+            split = rec.splits[N] = RayStorage.split_rays(self.ray_sources, N)
+        # a split without a remainder to draw (and none given) has the same range records every time
+        ranges_key = (N, _power_scale) if not split[1] and _N_list is None else None
         rng = None  # draws the remainder of the split: a seeded tracer repeats it with the seed
         if self.seed is not None and split[1]:
             rng = np.random.RandomState((int(self.seed) + 1000003 * int(_chunk)) % 2 ** 32)
         rays_obj = self.rays
         if _tail is not None:  # the split, the ranges and the powers live in a storage object without buffers
-            if self._tail_book is None:
-                self._tail_book = RayStorage()
-            rays_obj = self._tail_book
-        # unchanged sources and the same deterministic split as last time: the same range records
+            if rec.book is None:
+                rec.book = RayStorage()
+            rays_obj = rec.book
         rays_obj.init(self.ray_sources, N, nt, self.no_pol, _N_list=_N_list, _rng=rng, _power_scale=_power_scale,
-                      _split=split, _keep_ranges=fast is not None, _alloc=_tail is None)
+                      _split=split, _ranges=rec.ranges.get(ranges_key), _alloc=_tail is None)
         rays = rays_obj._rays_struct() if _tail is None else None
         # a seeded tracer repeats itself call for call; the chunks of one iterative render must differ
         seed = int(np.random.randint(0, 2 ** 31 - 1)) if self.seed is None else int(self.seed) + 1000003 * int(_chunk)
@@ -387,12 +396,14 @@ class Raytracer(Group):
                 tab = rays_obj._source_table(seed)
             else:
                 cache = self._source_cache
-                if fast is None or cache is None or cache[2] != _power_scale:
-                    skey = (repr(snap["RaySources"]), tuple(rays_obj._powers))
+                if not shortcut or cache is None or cache[2] != _power_scale:
+                    skey = (repr(rec.snap["RaySources"]), tuple(rays_obj._powers))
                     if cache is None or cache[0] != skey:
                         self._source_cache = cache = (skey, rays_obj._source_table(), _power_scale)
                 tab = cache[1]
             rng_c = rays_obj._source_ranges()
+            if ranges_key is not None:
+                rec.ranges[ranges_key] = rng_c
             # one synchronous call: launch, wait, counters in host memory (no device-to-host copy)
             if _tail is not None:
                 _tail.ensure(int(lib.ot_tail_capacity(N + _tail_room)))
@@ -430,11 +441,11 @@ class Raytracer(Group):
             raise RuntimeError("All ray divergences s need to be in positive z-divergence")
         self._show_messages(N)
         if _tail is None:  # (a render-only trace leaves `self.rays` and what is known about them alone)
-            snap["Rays"] = [rays_obj.N, rays_obj.Nt, rays_obj.no_pol]
-            self._last_trace_snapshot = snap
-        if fast is None and not writeable and _initial_rays is None and not rays_obj._has_function_orientation:
+            self._last_trace_snapshot = {**rec.snap, "Rays": [rays_obj.N, rays_obj.Nt, rays_obj.no_pol]}
+        if publish and _initial_rays is None and not rays_obj._has_function_orientation:
             # read the counter last: objects this call created itself (the end aperture of the element list) count too
-            self._fast = (_base.mutation_epoch(), self._structure(), snap, scene, splits, watch)
+            rec.epoch, rec.structure = _base.mutation_epoch(), self._structure()
+            self._record = rec
 
     # ---- detector (raytracer.py:881-1098) ----------------------------------------------------------------
     # ---- shared argument checks of the post-processing entry points ------------------------------------------
@@ -492,13 +503,8 @@ class Raytracer(Group):
             k = sp.get("detector_index", 0)
             det = self.detectors[k]
             if sp.get("pos") is not None:
-                # moving a detector changes nothing a trace depends on: the change counter (base.mutation_epoch) stays
-                # where it was, so that the next trace of an iterative render still takes its shortcut -- unless the
-                # detector shares its surface object with a tracing element (then the move IS a change of the scene)
-                epoch = _base._EPOCH[0]
+                # (a detector and its own surface are untracked: the next trace of an iterative render keeps its shortcut)
                 det.move_to(sp["pos"])
-                if all(det.surface is not ts for ts in self.tracing_surfaces):
-                    _base._EPOCH[0] = epoch
             dsurf = det.surface
 
             method = sp.get("projection_method", "Equidistant")
@@ -1061,7 +1067,7 @@ class Raytracer(Group):
         extentc = per_image(extent, "extent", isinstance(extent, list) and not isinstance(extent[0], (int, float)))
 
         n_sec = len(self.tracing_surfaces) + 2
-        if not self._scene_unchanged() and self._pretrace_check(min(N, 1000)):
+        if not self._scene_unchanged() and self._pretrace_check(min(N, 1000), self._geometry_key()):
             raise RuntimeError("Geometry checks failed. Tracing aborted. Check the warnings.")
         # Only the rays of the LAST chunk stay in the tracer (raytracer.py:1235-1267).  Every chunk before it is traced
         # render-only where the scene and the detector positions allow it: no section is stored, the living rays' last

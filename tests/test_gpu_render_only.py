@@ -206,6 +206,36 @@ def test_iterative_render_render_only_equals_stored_path(name, merge):
         assert abs(x.power() - y.power()) <= (3e-8 if merge else 1e-12) * y.power()
 
 
+@pytest.mark.parametrize("change", ["power", "remove_source"])
+def test_a_second_render_after_a_source_change_equals_the_stored_path(change):
+    """Render-only chunks take their split, range records and powers from the tracer's trace record, which a source change
+    replaces as a whole.  A second render of the same N after a source's power doubled, or after one of two sources was
+    removed, equals the same renders through the ray storage (the range records of the first render, with their powers
+    and source indices, were once reused)."""
+    with ot.global_options.no_warnings():
+        n = 400_000
+        out = {}
+        for mode in (True, False):
+            RT = scenes.c1_single_lens(ot, seed=5)
+            if change == "remove_source":  # (equal powers: a split without remainder, whose range records are kept)
+                RT.add(ot.RaySource(ot.Point(), divergence="Isotropic", div_angle=3, pos=[0.5, 0, -20],
+                                    spectrum=ot.LightSpectrum("Monochromatic", wl=600.)))
+            with settings(ITER_RAYS_STEP=n, ITER_RENDER_ONLY=mode, ITER_EXTENT_RAYS=1 << 60, ITER_MERGE_LAST=True):
+                first = RT.iterative_render(3 * n + 77, extent=[-2, 2, -2, 2])[0]
+                if change == "power":
+                    RT.ray_sources[0].power = 2 * RT.ray_sources[0].power
+                else:
+                    RT.remove(RT.ray_sources[0])
+                second = RT.iterative_render(3 * n + 77, extent=[-2, 2, -2, 2])[0]
+            out[mode] = (first, second)
+    for x, y in zip(out[True], out[False]):
+        same_image(x, y, tol=1e-7)
+        assert abs(x.power() - y.power()) <= 3e-8 * y.power()
+    if change == "power":
+        first, second = out[True]
+        assert abs(second.power() - 2 * first.power()) <= 1e-6 * second.power()
+
+
 def test_chunk_plan_and_speed_path_of_a_long_render():
     """Without ITER_RAYS_STEP: render-only chunks as large as the tail storage allows, then one stored chunk of
     ITER_LAST_RAYS; the result has the power of the plain chunked render to the ray statistics."""

@@ -487,3 +487,75 @@ def test_chunk_plan_of_an_iterative_render():
         assert RT._chunk_plan(500_000, 4, False) == [500_000]
     finally:
         ot.Raytracer.ITER_RAYS_STEP, ot.Raytracer.ITER_LAST_RAYS, ot.Raytracer.ITER_STORAGE_BYTES = old
+
+
+def _scene_with_detector():
+    RT = ot.Raytracer(outline=[-5, 5, -5, 5, -5, 40])
+    RT.add(ot.RaySource(ot.CircularSurface(r=1), divergence="None", s=[0, 0, 1], pos=[0, 0, 0]))
+    RT.add(ot.Lens(ot.SphericalSurface(r=3, R=20), ot.SphericalSurface(r=3, R=-20), de=0.2, pos=[0, 0, 10],
+                   n=ot.RefractionIndex("Constant", n=1.5)))
+    RT.add(ot.Aperture(ot.RingSurface(r=3, ri=0.5), pos=[0, 0, 15]))
+    RT.add(ot.Detector(ot.RectangularSurface(dim=[4, 4]), pos=[0, 0, 30]))
+    return RT
+
+
+def test_detector_moves_leave_the_change_counter_alone():
+    """A detector and its own surface feed no trace: moving one, directly or as `iterative_render` does
+    (`_detector_requests` with a position), is no scene change (base.mutation_epoch)."""
+    from optrace_amd.base import mutation_epoch
+    RT = _scene_with_detector()
+    det = RT.detectors[0]
+    assert not det._tracked and not det.surface._tracked
+    e0 = mutation_epoch()
+    det.move_to([0, 0, 25.])
+    assert mutation_epoch() == e0 and det.pos[2] == 25.
+    RT._detector_requests([dict(detector_index=0, pos=[0, 0, 28.])], no_rays=True)
+    assert mutation_epoch() == e0 and det.pos[2] == 28.
+
+
+def test_scene_changes_move_the_change_counter():
+    from optrace_amd.base import mutation_epoch
+    RT = _scene_with_detector()
+    for change in (lambda: RT.lenses[0].move_to([0, 0, 11.]),
+                   lambda: setattr(RT.ray_sources[0], "power", 2.),
+                   lambda: RT.add(ot.RaySource(ot.Point(), pos=[0, 0, 1])),
+                   lambda: RT.remove(RT.ray_sources[-1])):
+        e0 = mutation_epoch()
+        change()
+        assert mutation_epoch() > e0
+    assert RT.ray_sources[0].power == 2. and len(RT.ray_sources) == 1
+
+
+def test_surfaces_taken_from_a_detector_are_tracked():
+    """Elements copy the surfaces they are given; the copy is tracked like its new owner, whatever the original was."""
+    from optrace_amd.base import mutation_epoch
+    det = ot.Detector(ot.SphericalSurface(r=3, R=20), pos=[0, 0, 30])
+    lens = ot.Lens(det.surface, ot.SphericalSurface(r=3, R=-20), de=0.2, pos=[0, 0, 10],
+                   n=ot.RefractionIndex("Constant", n=1.5))
+    ap = ot.Aperture(det.surface, pos=[0, 0, 5])
+    assert lens.front._tracked and ap.surface._tracked and not det.surface._tracked
+    e0 = mutation_epoch()
+    lens.move_to([0, 0, 12.])
+    assert mutation_epoch() > e0
+
+
+def test_a_detector_that_shares_a_tracing_surface_moves_the_counter():
+    """The setup of test_gpu_edges.py: the detector's surface forced to be the aperture's surface object.  Moving the
+    detector then moves the aperture, a scene change."""
+    from optrace_amd.base import mutation_epoch
+    RT = _scene_with_detector()
+    RT.detectors[0].__dict__["front"] = RT.apertures[0].front
+    e0 = mutation_epoch()
+    RT._detector_requests([dict(detector_index=0, pos=[0, 0, 14.])], no_rays=True)
+    assert mutation_epoch() > e0 and RT.apertures[0].pos[2] == 14.
+
+
+def test_tracing_snapshot_collects_the_writeable_arrays():
+    """`tracing_snapshot(writeable)` lists the arrays a trace has to watch (the outline, small arrays like RaySource.s)
+    and returns the snapshot the no-argument call returns."""
+    RT = _scene_with_detector()
+    seen = []
+    snap = RT.tracing_snapshot(seen)
+    assert snap == RT.tracing_snapshot()
+    assert any(a is RT.outline for a in seen) and any(a is RT.ray_sources[0].s for a in seen)
+    assert all(a.flags.writeable for a in seen)

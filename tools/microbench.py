@@ -17,7 +17,7 @@ lib = _capi.load_library()
 with ot.global_options.no_warnings():
     RT = scenes.SCENES[scene_name][0](ot, no_pol=no_pol, seed=1)
     RT._geometry_checks()
-    sc = RT._compile()
+    sc = RT._compile(RT._geometry_key())
     RT.rays.init(RT.ray_sources, N, sc.nt, RT.no_pol)
 rays = RT.rays._rays_struct(); tab = RT.rays._source_table(); rng = RT.rays._source_ranges()
 msgs = torch.zeros(5 * sc.nt + 1, dtype=torch.int64, device="cuda")
