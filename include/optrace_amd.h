@@ -79,7 +79,7 @@ typedef struct ot_surface {
     double k;       /* CONIC/ASPHERE: conic constant                                             */
     double z_min;   /* absolute z range of the surface (Surface.z_min / z_max)                   */
     double z_max;
-    double coeff[OT_MAX_ASPH]; /* ASPHERE: a2, a4, ... [mm^-1, mm^-3, ...]                         */
+    double coeff[OT_MAX_ASPH]; /* ASPHERE: a2, a4, ... [mm^-1, mm^-3, ...] (more: OT_SURF_FLAG_ASPH_TABLE) */
     double normal[3]; /* TILTED: unit normal with normal[2] > 0 (TiltedSurface.normal)            */
     double sign;      /* DATA1D/2D: +1, or -1 after flip() (DataSurface2D._sign)                   */
     double offset;    /* DATA1D/2D: spline value at the centre, removed from every value (._offset) */
@@ -109,6 +109,14 @@ typedef struct ot_surface {
  * A position is on the surface if it is inside r (+ N_EPS) and its cell's bit is set; positions closer to the mask's
  * edge than one cell can therefore differ from the callable.  tab_len counts these doubles too. */
 #define OT_SURF_FLAG_MASK_TABLE 2
+/* ASPHERE with more than OT_MAX_ASPH coefficients (the reference sets no upper bound, aspheric_surface.py:23): with
+ * this flag `tab` holds all of them,
+ *     a2 | a4 | ... | a_(2 ncoeff)        tab_len = ncoeff doubles,
+ * and coeff[] is ignored (any ncoeff >= 1 may travel this way).  Host pointer, caller-owned, copied by the callee like
+ * the spline tables.  Without the flag an asphere is the call it always was: 1 <= ncoeff <= OT_MAX_ASPH coefficients in
+ * coeff[], `tab` unused.  ncoeff above OT_MAX_ASPH without the flag, the flag with a NULL `tab` or with
+ * tab_len != ncoeff are refused with a negative status; nothing is read through `tab` then. */
+#define OT_SURF_FLAG_ASPH_TABLE 4
 #define OT_SPL_K 4
 
 /* ---- media: RefractionIndex.__call__ refraction_index.py:62-169 ----------------------------- */

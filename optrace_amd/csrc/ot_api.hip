@@ -142,8 +142,13 @@ static int compile_surface(const ot_surface& s, SurfDev& d) {
         case OT_SURF_CONIC:
         case OT_SURF_ASPHERE: {
             if (s.R == 0.0 || !std::isfinite(s.R)) return fail(OT_ERR_INVALID, "surface: R must be finite and non-zero");
-            if (s.kind == OT_SURF_ASPHERE && (s.ncoeff < 1 || s.ncoeff > OT_MAX_ASPH))
-                return fail(OT_ERR_UNSUPPORTED, "asphere: ncoeff out of range");
+            const bool long_asph = s.kind == OT_SURF_ASPHERE && (s.flags & OT_SURF_FLAG_ASPH_TABLE);
+            if (s.kind == OT_SURF_ASPHERE && !long_asph && (s.ncoeff < 1 || s.ncoeff > OT_MAX_ASPH))
+                return fail(OT_ERR_UNSUPPORTED, "asphere: ncoeff out of range (more than OT_MAX_ASPH coefficients travel "
+                                                "in tab, OT_SURF_FLAG_ASPH_TABLE)");
+            if (long_asph && (s.ncoeff < 1 || !s.tab || s.tab_len != (int64_t)s.ncoeff))
+                return fail(OT_ERR_INVALID, "asphere: OT_SURF_FLAG_ASPH_TABLE needs tab with tab_len == ncoeff");
+            const double* const cf = long_asph ? s.tab : s.coeff;
             d.r_eps2 = std::pow(s.r + NE, 2.0);
             d.k = s.k;
             d.k1 = s.k + 1;
@@ -155,9 +160,12 @@ static int compile_surface(const ot_surface& s, SurfDev& d) {
             d.inv_rho = 1 / d.rho;
             d.two_inv_rho = 2 / d.rho;
             for (int j = 0; j < s.ncoeff && j < OT_MAX_ASPH; j++) {
-                d.coeff[j] = s.coeff[j];
-                d.dcoeff[j] = s.coeff[j] * (double)(2 * (j + 1));
+                d.coeff[j] = cf[j];
+                d.dcoeff[j] = cf[j] * (double)(2 * (j + 1));
             }
+            // more coefficients than the record holds: the device reads them from the surface's table (device_table);
+            // the host pointer marks that here, the caller swaps in the device copy
+            if (long_asph && s.ncoeff > OT_MAX_ASPH) d.tab = s.tab;
             // Surface.values outside the mask: pos_z + _values(r - N_EPS, 0) (surface.py:153-162)
             if (!d.flat) {
                 double re = s.r - NE;
@@ -169,7 +177,7 @@ static int compile_surface(const ot_surface& s, SurfDev& d) {
                     v = d.rho * (r * r) / (1 + std::sqrt(1 - d.k1rho2 * (r * r)));
                     double y = 0.0;
                     for (int j = s.ncoeff - 1; j >= 0; j--) {
-                        y = y * r + s.coeff[j];
+                        y = y * r + cf[j];
                         y = y * r + 0.0;
                     }
                     y = y * r + 0.0;
@@ -247,7 +255,32 @@ static int compile_surface(const ot_surface& s, SurfDev& d) {
     return OT_OK;
 }
 
-// A compiled surface for the leaf entry points: spline tables (if any) are uploaded for the duration of the call.
+// What goes into the device table of a compiled surface (d.tab != nullptr): the caller's spline tables as they are; for
+// an asphere with more than OT_MAX_ASPH coefficients the layout of ot_device.hpp::asph_poly_long, built here:
+// a[npad] | d[npad], d_j = a_j (2j + 2) as in SurfDev::dcoeff, zeros behind the last coefficient.
+struct DeviceTable {
+    std::vector<double> own;
+    const double* src = nullptr;
+    size_t len = 0;
+    DeviceTable(const ot_surface& s, const SurfDev& d) {
+        if (!d.tab) return;
+        if (s.kind == OT_SURF_ASPHERE) {
+            const int npad = asph_padded(s.ncoeff);
+            own.assign(2 * (size_t)npad, 0.0);
+            for (int j = 0; j < s.ncoeff; j++) {
+                own[j] = s.tab[j];
+                own[npad + j] = s.tab[j] * (double)(2 * (j + 1));
+            }
+            src = own.data();
+            len = own.size();
+        } else {
+            src = s.tab;
+            len = (size_t)s.tab_len;
+        }
+    }
+};
+
+// A compiled surface for the leaf entry points: its table (if any) is uploaded for the duration of the call.
 struct LeafSurface {
     SurfDev d;
     double* dev_tab = nullptr;
@@ -256,8 +289,10 @@ struct LeafSurface {
         st = stream;
         if (int rc = compile_surface(*surf, d)) return rc;
         if (d.tab) {
-            HIP_TRY(hipMalloc((void**)&dev_tab, sizeof(double) * surf->tab_len));
-            HIP_TRY(hipMemcpyAsync(dev_tab, surf->tab, sizeof(double) * surf->tab_len, hipMemcpyHostToDevice, st));
+            const DeviceTable t(*surf, d);
+            HIP_TRY(hipMalloc((void**)&dev_tab, sizeof(double) * t.len));
+            HIP_TRY(hipMemcpyAsync(dev_tab, t.src, sizeof(double) * t.len, hipMemcpyHostToDevice, st));
+            if (!t.own.empty()) HIP_TRY(hipStreamSynchronize(st));  // the source is a temporary of this call
             d.tab = dev_tab;
         }
         return OT_OK;
@@ -347,7 +382,8 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
             // flat data surfaces have a closed-form hit -- unless a mask_func bitmap has to be consulted
             if (!sf.flat || sf.mask_n != 0) lv = OT_HIT_SPLINE;
         } else if (sf.kind >= OT_SURF_ASPHERE && !sf.flat) {
-            lv = OT_HIT_ILLINOIS;
+            // an asphere with more coefficients than the record holds reads them from its table: the table-carrying level
+            lv = (sf.kind == OT_SURF_ASPHERE && sf.ncoeff > OT_MAX_ASPH) ? OT_HIT_SPLINE : OT_HIT_ILLINOIS;
         }
         hit_level = std::max(hit_level, lv);
     }
@@ -424,12 +460,15 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
     size_t o_lines = align_up(o_pool + sizeof(double) * pool_n);
     size_t o_cnt = align_up(o_lines + sizeof(double) * (line_tab.size() + 1));
     size_t o_stab = align_up(o_cnt + sizeof(unsigned int) * (size_t)OT_CNT_SLOTS * (OT_N_INFOS * nt + 1));
-    std::vector<size_t> stab_off(surfs.size(), 0);  // spline tables of data surfaces
+    std::vector<size_t> stab_off(surfs.size(), 0);  // spline tables of data surfaces, coefficients of long aspheres
+    std::vector<DeviceTable> stabs;
+    stabs.reserve(surfs.size());
     size_t total = o_stab;
     for (size_t i = 0; i < surfs.size(); i++) {
+        stabs.emplace_back(desc->surfaces[i], surfs[i]);
         if (!surfs[i].tab) continue;
         stab_off[i] = total;
-        total = align_up(total + sizeof(double) * (size_t)desc->surfaces[i].tab_len);
+        total = align_up(total + sizeof(double) * stabs[i].len);
     }
     total = align_up(total + 1);
 
@@ -461,7 +500,7 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
 
     for (size_t i = 0; i < surfs.size(); i++) {
         if (!surfs[i].tab) continue;
-        std::memcpy(host.data() + stab_off[i], desc->surfaces[i].tab, sizeof(double) * (size_t)desc->surfaces[i].tab_len);
+        std::memcpy(host.data() + stab_off[i], stabs[i].src, sizeof(double) * stabs[i].len);
         surfs[i].tab = (const double*)(blob + stab_off[i]);
     }
     std::memcpy(host.data() + o_hdr, &h, sizeof(h));

@@ -254,6 +254,34 @@ OT_DEV double asph_poly_deriv(SF& sf, double r) {  // polyval(polyder(..)) asphe
     return y;
 }
 
+// The same two polynomials for an asphere with more than OT_MAX_ASPH coefficients (OT_SURF_FLAG_ASPH_TABLE).  They live
+// in the surface's table, a[npad] | d[npad] with d_j = a_j (2j + 2) and npad = ncoeff rounded up to OT_ASPH_CHUNK, the
+// tail filled with zeros: Horner starts at the top of the padding, where y = (0 r + 0) r stays +0 for every finite r and
+// the first real step 0 r + a is a itself -- np.polyval with leading zero coefficients, the same arithmetic.  The table is
+// read through the constant address space with a wave-uniform index (the surface is the same for a whole wave, the loop
+// count comes from it), so a chunk arrives in scalar registers with one or two scalar loads and no lane loads anything.
+// Only table-carrying kernels (OT_HIT_SPLINE) contain this; a long asphere raises its scene to that level.
+#define OT_ASPH_CHUNK 4
+OT_HD int asph_padded(int ncoeff) { return (ncoeff + OT_ASPH_CHUNK - 1) / OT_ASPH_CHUNK * OT_ASPH_CHUNK; }
+
+// y after all coefficient steps: polyval over [a_2n, 0, ..., a_2, 0] (DERIV: the d_j); the caller of the sag multiplies
+// by r once more.  `+ 0` steps dropped as in AsphereSag.
+template <bool DERIV, class SF>
+OT_DEV double asph_poly_long(SF& sf, double r) {
+    const int npad = asph_padded(sf.ncoeff);
+    const OT_CONST double* c = (const OT_CONST double*)sf.tab + (DERIV ? npad : 0);
+    double y = 0.0;
+#pragma unroll 1
+    for (int j = npad - OT_ASPH_CHUNK; j >= 0; j -= OT_ASPH_CHUNK) {
+        const double c0 = c[j], c1 = c[j + 1], c2 = c[j + 2], c3 = c[j + 3];
+        y = (y * r + c3) * r;
+        y = (y * r + c2) * r;
+        y = (y * r + c1) * r;
+        y = (y * r + c0) * r;
+    }
+    return y;
+}
+
 // Surface._values relative to the centre: conic_surface.py:57, aspheric_surface.py:51
 template <int LEVEL = OT_HIT_SPLINE, class SF>
 OT_DEV double surf_values_rel(SF& sf, double x, double y, PatchCache* pc = nullptr) {
@@ -266,7 +294,10 @@ OT_DEV double surf_values_rel(SF& sf, double x, double y, PatchCache* pc = nullp
     double r = sqrt(x * x + y * y);
     double rr = r * r;
     double z = ot_div(sf.rho * rr, 1 + sqrt(1 - sf.k1rho2 * rr));
-    z += asph_poly(sf, r);
+    if (LEVEL >= OT_HIT_SPLINE && sf.ncoeff > OT_MAX_ASPH)  // wave-uniform
+        z += asph_poly_long<false>(sf, r) * r;
+    else
+        z += asph_poly(sf, r);
     return z;
 }
 
@@ -333,7 +364,10 @@ OT_DEV V3 surf_normal(SF& sf, double x, double y, PatchCache* pc = nullptr) {
     }
     double rm = ot_sqrt(dx * dx + dy * dy);
     double fr = ot_div(rm * sf.rho, ot_sqrt(1 - sf.k1rho2 * (rm * rm)));
-    fr += asph_poly_deriv(sf, rm);
+    if (LEVEL >= OT_HIT_SPLINE && sf.ncoeff > OT_MAX_ASPH)  // wave-uniform
+        fr += asph_poly_long<true>(sf, rm);
+    else
+        fr += asph_poly_deriv(sf, rm);
     const double irm = ot_rcp3(rm);
     double c = (rm > 0.0) ? ot_div_r(dx, rm, irm) : 1.0;
     double s = (rm > 0.0) ? ot_div_r(dy, rm, irm) : 0.0;
@@ -422,7 +456,8 @@ OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) 
 // polyval over [a_2n, 0, ..., a_2, 0, 0] is y = (y r + a) r per coefficient and one more `y r`; the reference's `+ 0`
 // steps only turn -0 into +0, which no later sum can see.
 // NC > 0: the surface has exactly NC coefficients (compile-time chain; find_hit picks the instance with one wave-uniform
-// switch outside the search loop).  NC = 0: any count, one jump into the unrolled chain per evaluation.
+// switch outside the search loop).  NC = 0: any count up to OT_MAX_ASPH, one jump into the unrolled chain per evaluation.
+// NC < 0: more than OT_MAX_ASPH coefficients, read from the surface's table (asph_poly_long; table-carrying kernels only).
 template <int NC, class SF>
 struct AsphereSag {
     SF& sf;
@@ -440,6 +475,8 @@ struct AsphereSag {
                 y_ = y_ * r + sf.coeff[j];
                 y_ = y_ * r;
             }
+        } else if (NC < 0) {
+            y_ = asph_poly_long<false>(sf, r);
         } else {
             // Horner from the highest coefficient the surface has: one wave-uniform jump into the unrolled chain.  (The
             // empty asm statements keep the steps from being turned into twelve always-executed select pairs.)
@@ -552,6 +589,7 @@ OT_DEV bool find_hit(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit, bool& 
     if (t1 < 0) t1 = -OT_C_EPS;
     const bool w0 = isfinite(t1) && isfinite(t2) && !((t2 - t1) < OT_C_EPS);
     if (sf.kind == OT_SURF_ASPHERE) {  // its own copies of the search: see AsphereSag
+        if (TABLES && sf.ncoeff > OT_MAX_ASPH) return find_hit_asphere<-1>(sf, p, s, t1, t2, w0, ph, hit, ill);
         switch (sf.ncoeff) {
             case 1: return find_hit_asphere<1>(sf, p, s, t1, t2, w0, ph, hit, ill);
             case 2: return find_hit_asphere<2>(sf, p, s, t1, t2, w0, ph, hit, ill);

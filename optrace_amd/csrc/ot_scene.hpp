@@ -38,6 +38,7 @@ struct SurfDev {
     double cpa, spa;          // cos(angle), sin(angle)                 slit_surface.py:83-84
     double coeff[OT_MAX_ASPH];   // a2, a4, ...
     double dcoeff[OT_MAX_ASPH];  // a_j * (2j+2): np.polyder coefficients
+    // (ncoeff > OT_MAX_ASPH: all of both in `tab` below, ot_device.hpp::asph_poly_long; these hold the first twelve)
     // tilted plane: unit normal and the slopes -n_x/n_z, -n_y/n_z      tilted_surface.py:69-72
     double nx, ny, nz, mx, my;
     // spline surfaces (DATA1D / DATA2D): sign, centre offset, knots per unit length (interval guess),

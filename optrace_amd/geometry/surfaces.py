@@ -492,11 +492,16 @@ class AsphericSurface(Surface):
     def _desc(self):
         d = Surface._desc(self)
         d.R, d.k = float(self.R), float(self.k)
-        if len(self.coeff) > _capi.OT_MAX_ASPH:
-            raise _capi.BackendError(f"AsphericSurface with more than {_capi.OT_MAX_ASPH} coefficients "
-                                     "is not supported by the device kernels.")
         d.ncoeff = len(self.coeff)
-        d.coeff[:len(self.coeff)] = [float(c) for c in self.coeff]
+        if len(self.coeff) > _capi.OT_MAX_ASPH:
+            # more than the descriptor's inline array holds: all of them travel in `tab` (OT_SURF_FLAG_ASPH_TABLE)
+            tab = np.ascontiguousarray(self.coeff, dtype=np.float64)
+            d.flags |= _capi.SURF_FLAG_ASPH_TABLE
+            d.tab = tab.ctypes.data_as(_capi.C.POINTER(_capi.C.c_double))
+            d.tab_len = tab.size
+            d._tab_keep = tab  # flip() replaces self.coeff: the descriptor keeps what it points to alive itself
+        else:
+            d.coeff[:len(self.coeff)] = [float(c) for c in self.coeff]
         return d
 
     def __setattr__(self, key, val):

@@ -62,6 +62,7 @@ class CompiledScene:
             elements.append(e)
 
         self.surfaces = (_capi.Surface * max(len(surfaces), 1))(*surfaces)
+        self._surface_descs = surfaces  # the array holds copies: the originals keep what their `tab` points to alive
         self.elements = (_capi.Element * max(len(elements), 1))(*elements)
         self.media = (_capi.Medium * max(len(media), 1))(*media)
         self.filters = (_capi.Filter * max(len(filters), 1))(*filters)
