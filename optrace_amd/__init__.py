@@ -20,6 +20,7 @@ from .render_image import RenderImage
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
 from .convolve import convolve
+from .tma import TMA
 from . import presets, misc
 
 __version__ = "0.1.0"

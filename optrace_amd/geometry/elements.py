@@ -18,6 +18,7 @@ import numpy as np
 from ..base import BaseClass, check_type, touch
 from ..refraction_index import RefractionIndex
 from ..spectrum import TransmissionSpectrum
+from ..tma import TMA
 from .._warn import warning
 from .surfaces import Surface, Point, Line, CircularSurface, AsphericSurface
 
@@ -188,6 +189,11 @@ class Lens(Element):
         """Gap between the z ranges of the two surfaces (negative if they overlap)."""
         return float(self.back.z_min) - float(self.front.z_max)
 
+    def tma(self, wl: float = 555., n0: RefractionIndex = None) -> TMA:
+        """Paraxial analysis of this lens alone (lens.py:92-102).  The lens does not know the medium in front of it:
+        n0 (default: 1); the medium behind it is its n2."""
+        return TMA([self], wl, n0)
+
     def __setattr__(self, key, val):
         if key == "n":
             check_type(key, val, RefractionIndex)
@@ -330,6 +336,10 @@ class Group(BaseClass):
             x, y, z = el.pos
             el.rotate(angle)
             el.move_to([x0 + c * (x - x0) - s * (y - y0), y0 + s * (x - x0) + c * (y - y0), z])
+
+    def tma(self, wl: float = 555.) -> TMA:
+        """Paraxial analysis of the group's lenses in its ambient medium n0 (group.py:142-150): a snapshot."""
+        return TMA(self.lenses, wl=wl, n0=self.n0)
 
     def flip(self, y0: float = 0, z0: float = None) -> None:
         """Turn the group around the axis through (y0, z0) parallel to x (z0: middle of the z extent).  The media
