@@ -14,13 +14,14 @@ from .spectrum import Spectrum, LightSpectrum, TransmissionSpectrum
 from .geometry import (Surface, CircularSurface, RingSurface, RectangularSurface, SlitSurface, ConicSurface,
                        SphericalSurface, AsphericSurface, Point, Line, Element, Lens, IdealLens, Aperture,
                        Filter, Detector, Group, RaySource, TiltedSurface, DataSurface1D, DataSurface2D,
-                       FunctionSurface1D, FunctionSurface2D)
+                       FunctionSurface1D, FunctionSurface2D, PointMarker, LineMarker)
 from .image import RGBImage, GrayscaleImage, ScalarImage
 from .render_image import RenderImage
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
 from .convolve import convolve
 from .tma import TMA
+from .load import load_agf, load_zmx
 from . import presets, misc
 
 __version__ = "0.1.0"

@@ -268,6 +268,53 @@ class Detector(_SingleSurface):
         Element.__setattr__(self, key, val)
 
 
+class _Marker(Element):
+    """Annotations of a scene (geometry/marker/): a point or a line with a text.  Nothing a trace depends on: untracked
+    like a detector (base.mutation_epoch) and never compiled into a scene."""
+
+    _tracked = False
+    _FACTORS: tuple = ()
+
+    @staticmethod
+    def _shape(cls, **kwargs):
+        """A Point or Line that is untracked from its first assignment on: making a marker is no scene change either."""
+        shape = cls.__new__(cls)
+        shape.__dict__["_tracked"] = False
+        shape.__init__(**kwargs)
+        return shape
+
+    def __setattr__(self, key, val):
+        if key in self._FACTORS:
+            check_type(key, val, (float, int))
+        elif key == "label_only":
+            check_type(key, val, bool)
+        Element.__setattr__(self, key, val)
+
+
+class PointMarker(_Marker):
+    """A point and / or a text at a position (point_marker.py:10-62); label_only: the text without the point."""
+
+    _FACTORS = ("text_factor", "marker_factor")
+
+    def __init__(self, desc: str, pos, text_factor: float = 1., marker_factor: float = 1., label_only: bool = False,
+                 **kwargs) -> None:
+        self.marker_factor, self.text_factor, self.label_only = marker_factor, text_factor, label_only
+        Element.__init__(self, self._shape(Point), pos, desc=desc, **kwargs)
+        self._new_lock = True
+
+
+class LineMarker(_Marker):
+    """A line of radius r at an angle in the xy plane, with a text (line_marker.py:10-56)."""
+
+    _FACTORS = ("text_factor", "line_factor")
+
+    def __init__(self, r: float, pos, desc: str = "", angle: float = 0, text_factor: float = 1.,
+                 line_factor: float = 1., **kwargs) -> None:
+        self.text_factor, self.line_factor = text_factor, line_factor
+        Element.__init__(self, self._shape(Line, r=r, angle=angle), pos, desc=desc, **kwargs)
+        self._new_lock = True
+
+
 class Group(BaseClass):
     """Container of elements with an ambient index n0 (group.py:18-308)."""
 
@@ -363,14 +410,13 @@ class Group(BaseClass):
     def _list_for(self, el):
         from .ray_source import RaySource
         for cls, name in ((Aperture, "apertures"), (Filter, "filters"), (RaySource, "ray_sources"),
-                          (Detector, "detectors"), (Lens, "lenses")):
+                          (Detector, "detectors"), (Lens, "lenses"), (_Marker, "markers")):
             if isinstance(el, cls):
                 return getattr(self, name)
         return None
 
     def add(self, el) -> None:
         """Add an element, a list of elements or the elements of another Group (whose ambient index is taken over)."""
-        touch()
         if isinstance(el, list):
             for item in el:
                 self.add(item)
@@ -388,10 +434,11 @@ class Group(BaseClass):
         if target is None:
             raise TypeError(f"Unsupported element type {type(el).__name__}.")
         target.append(el)
+        if el._tracked:  # (detectors and markers feed no trace: base.mutation_epoch)
+            touch()
 
     def remove(self, el) -> bool:
         """Remove an element (by identity), a list of elements or a Group's elements; True if anything was removed."""
-        touch()
         if isinstance(el, (list, Group)):
             items = list(el) if isinstance(el, list) else el._elements
             return any([self.remove(item) for item in items])
@@ -401,6 +448,8 @@ class Group(BaseClass):
             kept = [x for x in lst if x is not el]
             found = found or len(kept) != len(lst)
             lst[:] = kept
+        if found and getattr(el, "_tracked", True):
+            touch()
         return found
 
     def has(self, el) -> bool:

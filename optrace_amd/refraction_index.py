@@ -177,3 +177,67 @@ class RefractionIndex(Spectrum):
         elif key == "func" and callable(val) and np.min(val(wavelengths(1000), **self.func_args)) < 1:
             raise ValueError("Function func needs to output values >= 1 over the whole visible range.")
         super().__setattr__(key, val)
+
+
+# ---- host evaluation at single wavelengths (paraxial analysis, catalogue checks: nothing per ray) ----------------------
+def _sellmeier(c, w, first: float = 1.0, pairs: int = 3):
+    return np.sqrt(sum((c[2 * j] * w / (w - c[2 * j + 1]) for j in range(pairs)), first))
+
+
+def _herzberger(c, w, L):
+    return c[0] + c[1] * L + c[2] * L ** 2 + c[3] * w + c[4] * w ** 2 + c[5] * w ** 3
+
+
+# the dispersion formulas once more for the host, n(w), w = (wavelength in um)**2, as ot_device.hpp::medium_n has them (refraction_index.py:102-148);
+# Conrady's, in the wavelength itself, is in `index_at`
+_HOST_FORMULAS = {
+    "Cauchy": lambda c, w: c[0] + c[1] / w + c[2] / w ** 2 + c[3] / w ** 3,
+    "Sellmeier1": lambda c, w: _sellmeier(c, w),
+    "Sellmeier2": lambda c, w: np.sqrt(1 + c[0] + c[1] * w / (w - c[2] ** 2) + c[3] / (w - c[4] ** 2)),
+    "Sellmeier3": lambda c, w: _sellmeier(c, w, pairs=4),
+    "Sellmeier4": lambda c, w: np.sqrt(c[0] + c[1] * w / (w - c[2]) + c[3] * w / (w - c[4])),
+    "Sellmeier5": lambda c, w: _sellmeier(c, w, pairs=5),
+    "Schott": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] / w + c[3] / w ** 2 + c[4] / w ** 3 + c[5] / w ** 4),
+    "Herzberger": lambda c, w: _herzberger(c, w, 1 / (w - 0.028)),
+    "Handbook of Optics 1": lambda c, w: np.sqrt(c[0] + c[1] / (w - c[2]) - c[3] * w),
+    "Handbook of Optics 2": lambda c, w: np.sqrt(c[0] + c[1] * w / (w - c[2]) - c[3] * w),
+    "Extended": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] / w + c[3] / w ** 2 + c[4] / w ** 3 + c[5] / w ** 4
+                                     + c[6] / w ** 5 + c[7] / w ** 6),
+    "Extended2": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] / w + c[3] / w ** 2 + c[4] / w ** 3 + c[5] / w ** 4
+                                      + c[6] * w ** 2 + c[7] * w ** 3),
+    "Extended3": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] * w ** 2 + c[3] / w + c[4] / w ** 2 + c[5] / w ** 3
+                                      + c[6] * w ** 4 + c[7] * w ** 5 + c[8] / w ** 6),
+}
+
+
+def index_at(medium: RefractionIndex, wl: float) -> float:
+    """n of `medium` at one wavelength [nm], in float64 on the host, with the errors of `RefractionIndex.__call__`."""
+    x = np.asarray_chkfinite(wl, dtype=np.float64)
+    kind = medium.spectrum_type
+    w = (x * 1e-3) ** 2
+    if kind in ("Constant", "Function", "Data"):
+        if kind == "Data" and not medium._wls[0] <= x <= medium._wls[-1]:
+            raise RuntimeError(f"Wavelength range [{float(x):.5g}, {float(x):.5g}] larger than data range"
+                               f" [{medium._wls[0]}, {medium._wls[-1]}] for this material.")
+        n = Spectrum._eval_host(medium, x)
+    elif kind == "Abbe":
+        if medium.V is None:
+            raise TypeError("Abbe number V needs to be provided for n_type='Abbe'")
+        A, B, d = medium._abbe_AB()
+        n = A + B / (w - d)
+    else:
+        if medium.coeff is None:
+            raise TypeError(f"coefficient variable 'coeff' needs to be provided for n_type='{kind}'.")
+        c, um = medium.coeff, x * 1e-3
+        n = c[0] + c[1] / um + c[2] / um ** 3.5 if kind == "Conrady" else _HOST_FORMULAS[kind](c, w)
+    n = float(n)
+    if n < 1:
+        raise RuntimeError(f"Refraction index below 1 with value {n:.4g} at {float(x):.4g}nm.")
+    return n
+
+
+def abbe_at(medium: RefractionIndex, lines: list) -> float:
+    """Abbe number of `medium` at three lines [nm] (short, centre, long) from `index_at`; inf without dispersion."""
+    n_short, n_centre, n_long = (index_at(medium, wl) for wl in lines)
+    spread = n_short - n_long
+    return (n_centre - 1) / spread if spread else float("inf")

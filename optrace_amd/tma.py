@@ -8,9 +8,9 @@ The vectors are (height, angle) columns, a system matrix maps the front vertex p
 `_steps` keeps every factor of it together with the distance from the front vertex at which that factor ends: the pupil
 methods cut the chain there into the group in front of the stop and the group behind it.
 
-Refraction indices are evaluated here, on the host, at the one wavelength of the analysis in float64
-(`index_at`): `RefractionIndex.__call__` is a device call on wavelengths stored as float32, which a paraxial analysis
-must not need and whose rounding of the wavelength the reference's analysis does not have.
+Refraction indices are evaluated on the host, at the one wavelength of the analysis in float64
+(`refraction_index.index_at`): `RefractionIndex.__call__` is a device call on wavelengths stored as float32, which a
+paraxial analysis must not need and whose rounding of the wavelength the reference's analysis does not have.
 """
 from __future__ import annotations
 
@@ -18,66 +18,9 @@ import numpy as np
 
 from .base import BaseClass, check_type, check_not_below, check_not_above
 from .options import global_options
-from .refraction_index import RefractionIndex
-from .spectrum import Spectrum
+from .refraction_index import RefractionIndex, index_at
 
 _NAN2 = (float("nan"), float("nan"))
-
-
-def _sellmeier(c, w, first: float = 1.0, pairs: int = 3):
-    return np.sqrt(sum((c[2 * j] * w / (w - c[2 * j + 1]) for j in range(pairs)), first))
-
-
-def _herzberger(c, w, L):
-    return c[0] + c[1] * L + c[2] * L ** 2 + c[3] * w + c[4] * w ** 2 + c[5] * w ** 3
-
-
-# dispersion formulas n(w), w = (wavelength in um)**2, as ot_device.hpp::medium_n has them (refraction_index.py:102-148);
-# Conrady's, in the wavelength itself, is in `index_at`
-_FORMULAS = {
-    "Cauchy": lambda c, w: c[0] + c[1] / w + c[2] / w ** 2 + c[3] / w ** 3,
-    "Sellmeier1": lambda c, w: _sellmeier(c, w),
-    "Sellmeier2": lambda c, w: np.sqrt(1 + c[0] + c[1] * w / (w - c[2] ** 2) + c[3] / (w - c[4] ** 2)),
-    "Sellmeier3": lambda c, w: _sellmeier(c, w, pairs=4),
-    "Sellmeier4": lambda c, w: np.sqrt(c[0] + c[1] * w / (w - c[2]) + c[3] * w / (w - c[4])),
-    "Sellmeier5": lambda c, w: _sellmeier(c, w, pairs=5),
-    "Schott": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] / w + c[3] / w ** 2 + c[4] / w ** 3 + c[5] / w ** 4),
-    "Herzberger": lambda c, w: _herzberger(c, w, 1 / (w - 0.028)),
-    "Handbook of Optics 1": lambda c, w: np.sqrt(c[0] + c[1] / (w - c[2]) - c[3] * w),
-    "Handbook of Optics 2": lambda c, w: np.sqrt(c[0] + c[1] * w / (w - c[2]) - c[3] * w),
-    "Extended": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] / w + c[3] / w ** 2 + c[4] / w ** 3 + c[5] / w ** 4
-                                     + c[6] / w ** 5 + c[7] / w ** 6),
-    "Extended2": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] / w + c[3] / w ** 2 + c[4] / w ** 3 + c[5] / w ** 4
-                                      + c[6] * w ** 2 + c[7] * w ** 3),
-    "Extended3": lambda c, w: np.sqrt(c[0] + c[1] * w + c[2] * w ** 2 + c[3] / w + c[4] / w ** 2 + c[5] / w ** 3
-                                      + c[6] * w ** 4 + c[7] * w ** 5 + c[8] / w ** 6),
-}
-
-
-def index_at(medium: RefractionIndex, wl: float) -> float:
-    """n of `medium` at one wavelength [nm], in float64 on the host, with the errors of `RefractionIndex.__call__`."""
-    x = np.asarray_chkfinite(wl, dtype=np.float64)
-    kind = medium.spectrum_type
-    w = (x * 1e-3) ** 2
-    if kind in ("Constant", "Function", "Data"):
-        if kind == "Data" and not medium._wls[0] <= x <= medium._wls[-1]:
-            raise RuntimeError(f"Wavelength range [{float(x):.5g}, {float(x):.5g}] larger than data range"
-                               f" [{medium._wls[0]}, {medium._wls[-1]}] for this material.")
-        n = Spectrum._eval_host(medium, x)
-    elif kind == "Abbe":
-        if medium.V is None:
-            raise TypeError("Abbe number V needs to be provided for n_type='Abbe'")
-        A, B, d = medium._abbe_AB()
-        n = A + B / (w - d)
-    else:
-        if medium.coeff is None:
-            raise TypeError(f"coefficient variable 'coeff' needs to be provided for n_type='{kind}'.")
-        c, um = medium.coeff, x * 1e-3
-        n = c[0] + c[1] / um + c[2] / um ** 3.5 if kind == "Conrady" else _FORMULAS[kind](c, w)
-    n = float(n)
-    if n < 1:
-        raise RuntimeError(f"Refraction index below 1 with value {n:.4g} at {float(x):.4g}nm.")
-    return n
 
 
 def _shift(dz: float) -> np.ndarray:
