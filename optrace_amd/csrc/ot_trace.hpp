@@ -140,6 +140,31 @@ OT_DEV void refraction_polarization(const V3& n, const V3& s, const V3& s_, doub
     }
 }
 
+// __compute_polarization for a surface with the same medium on both sides (N == 1, e.g. a lens whose n2 is its own n).
+// There s' = s - q n with q = ns - sqrt(ns^2), which is zero or one rounding error: where it is not zero the reference
+// builds its basis from ps = normalize(s' x s), a vector of rounding noise with an arbitrary direction (not even
+// perpendicular to s), so A_ts^2 + A_tp^2 != |pol|^2 and the pol it stores is bent.  The result depends on every bit of
+// s' x s: this is the reference's own operation order without contraction (the file's default; cross3, normalize3 and
+// dot3 of ot_device.hpp are bit-exact), not the plane of incidence that refraction_polarization uses.
+OT_DEV void same_medium_polarization(const V3& s, const V3& s_, const RayState& r, float& npx, float& npy, float& npz,
+                                     double& A_ts2, double& A_tp2) {
+    const bool mask = (s.x != s_.x) || (s.y != s_.y) || (s.z != s_.z);
+    A_ts2 = 0.5;
+    A_tp2 = 0.5;
+    if (mask) {
+        const V3 ps = normalize3(cross3(s_, s));
+        const V3 pp = cross3(ps, s);
+        const V3 pol = {(double)r.polx, (double)r.poly, (double)r.polz};
+        const double A_ts = dot3(ps, pol), A_tp = dot3(pp, pol);
+        const V3 pp_ = cross3(ps, s_);
+        npx = (float)(ps.x * A_ts + pp_.x * A_tp);
+        npy = (float)(ps.y * A_ts + pp_.y * A_tp);
+        npz = (float)(ps.z * A_ts + pp_.z * A_tp);
+        A_ts2 = A_ts * A_ts;
+        A_tp2 = A_tp * A_tp;
+    }
+}
+
 // Fresnel power transmission from squared amplitudes (see fresnel_T)
 OT_DEV double fresnel_T2(double n1, double n2, double ns, double W, double A_ts2, double A_tp2) {
 #pragma clang fp contract(fast)
@@ -166,7 +191,10 @@ OT_DEV bool refract(SF& sf, RayState& r, const V3& pn, float& wn, float& npx, fl
     V3 s_ = {s.x * N - n.x * q, s.y * N - n.y * q, s.z * N - n.z * q};
 
     double A_ts2, A_tp2;
-    refraction_polarization<POL>(n, s, s_, ns, W, N, q, r, npx, npy, npz, A_ts2, A_tp2);
+    if (POL && N == 1.0)
+        same_medium_polarization(s, s_, r, npx, npy, npz, A_ts2, A_tp2);
+    else
+        refraction_polarization<POL>(n, s, s_, ns, W, N, q, r, npx, npy, npz, A_ts2, A_tp2);
     double T = fresnel_T2(n1, n2, ns, W, A_ts2, A_tp2);
     bool tir = !isfinite(W);
     if (tir) T = 0;

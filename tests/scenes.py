@@ -359,6 +359,201 @@ def random_scene(ot, scene_seed, **rt_args):
 
 
 
+# ---- detector stage: every detector kind at every placement (tests/golden/detectors.npz) ---------------------------
+def front_focal_distance(surfaces, wl=555.):
+    """Paraxial distance of the front focal point in front of the first vertex.  surfaces: (R or inf, index behind the surface,
+    distance to the next vertex); the system stands in air."""
+    M = np.eye(2)
+    n_before = 1.0
+    for R, n_after, gap in surfaces:
+        power = 0.0 if np.isinf(R) else (n_after - n_before) / R
+        M = np.array([[1, 0], [-power / n_after, n_before / n_after]]) @ M
+        M = np.array([[1, gap], [0, 1]]) @ M
+        n_before = n_after
+    return -M[1, 1] / M[1, 0]  # a ray (s t, t) at the first vertex leaves with angle t (C s + D) = 0
+
+
+def objective(ot, sources="image", gap=0.0001, stop=False, z_end=300., **rt_args):
+    """The doublet of tests/test_tracer_special.py:459-526 (test_hit_dector_many_surfaces_different_detector_surfaces): flint
+    plate with a spherical back against a crown lens with a conic back, the object 0.6 mm in front of the front focal point.
+    (The glasses of the reference's preset catalogue are stood in for by Abbe models of their n_d / V_d; the object is a
+    synthetic picture.)  sources="pair": two small sources instead (a Lambertian disc in the object plane and an off-axis point 0.3 mm in front of it), so that
+    `source_index` selects something; `gap`: distance of the two lenses' facing vertices; `stop`: a ring stop in the middle
+    of that gap (needs a gap of about 1 mm).  -> Raytracer with lenses [flint, crown]."""
+    RT = ot.Raytracer(outline=[-10, 10, -10, 10, -10, z_end], **rt_args)
+    if sources == "image":
+        RT.add(ot.RaySource(ot.RGBImage(synthetic_rgb_image(), [0.2, 0.2]), divergence="Lambertian", pos=[0, 0, 0],
+                            s=[0, 0, 1], div_angle=27))
+    else:
+        RT.add(ot.RaySource(ot.CircularSurface(r=0.1), divergence="Lambertian", div_angle=20, pos=[0, 0, 0], s=[0, 0, 1],
+                            spectrum=ot.LightSpectrum("Lines", lines=[486.1327, 589.2938, 656.272], line_vals=[1, 2, 1]),
+                            polarization="x"))
+        RT.add(ot.RaySource(ot.Point(), divergence="Isotropic", div_angle=18, pos=[0.15, -0.1, -0.3], s=[0, 0, 1],
+                            spectrum=ot.LightSpectrum("Monochromatic", wl=520.), polarization="Uniform", power=0.7))
+    flint, crown = ot.RefractionIndex("Abbe", n=1.72825, V=28.41), ot.RefractionIndex("Abbe", n=1.713, V=53.83)
+    R1, R2 = 7.74, -7.29
+    s = front_focal_distance([(np.inf, float(flint(555.)), 0.5), (-R2, float(flint(555.)), 0.0001),
+                              (-R2, float(crown(555.)), 5.3), (-R1, 1.0, 0.0)])
+    z1 = 0.6 + s + 0.5  # the front focal point 0.6 mm behind the object
+    RT.add(ot.Lens(ot.CircularSurface(r=5.5), ot.SphericalSurface(r=5.5, R=-R2), d1=0.5, d2=0, pos=[0, 0, z1], n=flint,
+                   n2=flint))
+    if stop:
+        RT.add(ot.Aperture(ot.RingSurface(r=2.6, ri=1.9), pos=[0, 0, z1 + gap / 2]))
+    RT.add(ot.Lens(ot.SphericalSurface(r=5.5, R=-R2), ot.ConicSurface(r=5.5, R=-R1, k=-0.55), d1=0, d2=5.3,
+                   pos=[0, 0, z1 + gap], n=crown))
+    return RT
+
+
+def detector_objective(ot, **rt_args):
+    """Fixture scene "objective": the doublet with its lenses 1.2 mm apart, a ring stop between them that takes the rays
+    between 1.9 and 2.6 mm from the axis, two sources, polarisation on."""
+    return objective(ot, sources="pair", gap=1.2, stop=True, z_end=40., **rt_args)
+
+
+def _det_data2d(X, Y):
+    return X ** 2 / 20 + Y ** 2 / 14 + 0.02 * np.sin(2 * X)
+
+
+def detector_numeric(ot, **rt_args):
+    """Fixture scene "numeric": a plane filter, an aspheric lens and a lens with a DataSurface2D front, then a slit aperture:
+    sections that end at hits of the numeric search, and one section more than the objective has.  Traced with no_pol=True."""
+    RT = ot.Raytracer(outline=[-10, 10, -10, 10, -10, 40], **rt_args)
+    RT.add(ot.RaySource(ot.CircularSurface(r=1.5), divergence="Lambertian", div_angle=10, pos=[0.2, -0.1, -6], s=[0, 0, 1],
+                        spectrum=ot.LightSpectrum("Rectangle", wl0=450., wl1=650.)))
+    with ot.global_options.no_warnings():
+        front = ot.AsphericSurface(r=4, R=12, k=-0.8, coeff=[2e-3, -4e-5, 3e-7])
+        back = ot.AsphericSurface(r=4, R=-15, k=0.3, coeff=[-1e-3, 2e-5])
+    RT.add(ot.Filter(ot.CircularSurface(r=4), pos=[0, 0, -3], spectrum=ot.TransmissionSpectrum("Constant", val=0.9)))
+    RT.add(ot.Lens(front, back, de=0.4, pos=[0, 0, 0], n=ot.RefractionIndex("Constant", n=1.5)))
+    xy = np.linspace(-4.0, 4.0, 160)
+    X, Y = np.meshgrid(xy, xy)
+    RT.add(ot.Lens(ot.DataSurface2D(r=4.0, data=_det_data2d(X, Y)), ot.CircularSurface(r=4.0), de=0.5, pos=[0, 0, 8],
+                   n=ot.RefractionIndex("Constant", n=1.6)))
+    RT.add(ot.Aperture(ot.SlitSurface(dim=[9, 9], dimi=[2.4, 3.4]), pos=[0, 0, 14]))
+    return RT
+
+
+DETECTOR_SCENES = {"objective": (detector_objective, 440, {}), "numeric": (detector_numeric, 300, dict(no_pol=True))}
+
+
+def detector_kinds(ot) -> dict:
+    """name -> surface for every surface class a Detector accepts (detector.py:39-41 refuses data, function and aspheric
+    surfaces: `detector_refused`), all of radius 3.5 (the rectangles 6 x 5).  Flat, conic and spherical ones have a
+    closed-form hit; the tilted ones are the detectors that take the numeric hit search."""
+    r = 3.5
+    z = {}
+    z["circle"] = ot.CircularSurface(r=r)
+    z["ring"] = ot.RingSurface(r=r, ri=0.8)
+    z["rect"] = ot.RectangularSurface(dim=[6.0, 5.0])
+    z["slit"] = ot.SlitSurface(dim=[6.0, 5.0], dimi=[0.4, 1.2])
+    z["conic_k2"] = ot.ConicSurface(r=r, R=-10, k=2)
+    z["conic_hyp"] = ot.ConicSurface(r=r, R=9, k=-2.5)
+    z["sphere_pos"] = ot.SphericalSurface(r=r, R=8)
+    z["sphere_neg"] = ot.SphericalSurface(r=r, R=-6)
+    z["tilted"] = ot.TiltedSurface(r=r, normal_sph=[10., 40.])
+    z["tilted_y"] = ot.TiltedSurface(r=r, normal=[0, -0.45, np.sqrt(1 - 0.45 ** 2)])
+    z["tilted_steep"] = ot.TiltedSurface(r=r, normal=[2, 0, 1])  # spans all surfaces of the objective when put in its middle
+    # tests/test_tracer_special.py:289-316 (test_detector_ill_conditioned): a tilted detector whose z_max has been made wrong
+    # has no root inside the search bracket for rays that miss its disc -- the one way to an ill-conditioned detector hit
+    t = ot.TiltedSurface(r=1.5, normal=[0, -np.sin(1.0), np.cos(1.0)])
+    t._lock = False
+    t.z_max = 0.4 * t.z_max
+    t._lock = True
+    z["tilted_ill"] = t
+    return z
+
+
+def detector_refused(ot) -> dict:
+    """name -> surface of the classes a Detector does not take."""
+    r = 3.5
+    z = {}
+    with ot.global_options.no_warnings():
+        z["asphere"] = ot.AsphericSurface(r=r, R=12, k=-0.8, coeff=[2e-3, -4e-5])
+    rr = np.linspace(0, r, 240)
+    z["data1d"] = ot.DataSurface1D(r=r, data=10 - np.sqrt(100 - rr ** 2))
+    xy = np.linspace(-r, r, 140)
+    X, Y = np.meshgrid(xy, xy)
+    z["data2d"] = ot.DataSurface2D(r=r, data=_det_data2d(X, Y))
+    z["func1d"] = ot.FunctionSurface1D(r=r, func=lambda q: q ** 2 / 16 + 0.001 * q ** 4)
+    z["func2d"] = ot.FunctionSurface2D(r=r, func=_func2d, deriv_func=_func2d_deriv)
+    z["func2d_mask"] = ot.FunctionSurface2D(r=r, func=_paraboloid, mask_func=_window)
+    return z
+
+
+DETECTOR_CLOSED = ["circle", "ring", "rect", "slit", "conic_k2", "conic_hyp", "sphere_pos", "sphere_neg"]
+"""kinds with a closed-form hit; the others take the numeric hit search"""
+DETECTOR_NUMERIC = ["tilted", "tilted_y", "tilted_steep", "tilted_ill"]
+DETECTOR_PLACEMENTS = ["behind", "between", "stop", "inside", "source", "front", "end", "beyond", "lateral"]
+SPHERE_PROJECTIONS = ["Equidistant", "Orthographic", "Equal-Area", "Stereographic"]
+
+
+def detector_position(RT, surf, placement: str) -> list:
+    """Where a detector with surface `surf` goes for `placement` in a fixture scene (lenses [first, second], one aperture).
+      behind   4 mm behind the last surface          between  between the two lenses (behind the stop if it is there)
+      stop     the aperture's plane in the middle of the detector's z-range, so that rays which died there end inside it (a
+               flat detector has no z-range: 1e-3 mm behind the aperture -- the dead rays end just in front of it)
+      inside   in the second lens, between its faces  source   in the plane of the (first) source
+      front    10 mm in front of the sources           end      1e-6 mm in front of the outline's far face
+      offaxis  1 mm behind the first source, 1.8 mm off the axis
+      beyond   10 mm behind the outline               lateral  as `behind`, displaced so that part of the beam misses"""
+    L0, L1 = RT.lenses[:2]
+    ap = RT.apertures[0]
+    lo, hi = surf.z_min - surf.pos[2], surf.z_max - surf.pos[2]
+    z_last = max(el.extent[5] for el in list(RT.lenses) + list(RT.apertures))
+    zb, zf, za = L0.back.pos[2], L1.front.pos[2], ap.pos[2]
+    z_src = min(rs.pos[2] for rs in RT.ray_sources)
+    if placement == "behind":
+        return [0, 0, z_last + 4.0]
+    if placement == "between":
+        return [0, 0, 0.5 * ((za if zb < za < zf else zb) + zf)]
+    if placement == "stop":
+        return [0, 0, za + 1e-3 if lo == hi else za - 0.5 * (lo + hi)]
+    if placement == "inside":
+        return [0, 0, 0.5 * (L1.front.pos[2] + L1.back.pos[2])]
+    if placement == "source":
+        return [0, 0, RT.ray_sources[0].pos[2]]
+    if placement == "front":
+        return [0, 0, z_src - 10.0]
+    if placement == "end":
+        return [0, 0, RT.outline[5] - 1e-6]
+    if placement == "beyond":
+        return [0, 0, RT.outline[5] + 10.0]
+    if placement == "lateral":
+        return [1.6, -0.6, z_last + 4.0]
+    if placement == "offaxis":  # (the ill-conditioned detector: every ray starts before it and most pass its disc)
+        return [0, -1.8, RT.ray_sources[0].pos[2] + 1.0]
+    raise ValueError(placement)
+
+
+def add_detectors(ot, RT) -> dict:
+    """One detector per kind of `detector_kinds`, parked behind the last surface.  -> kind -> detector index."""
+    idx = {}
+    for kind, surf in detector_kinds(ot).items():
+        idx[kind] = len(RT.detectors)
+        RT.add(ot.Detector(surf, pos=detector_position(RT, surf, "behind")))
+    return idx
+
+
+def detector_records(scene: str) -> list:
+    """(kind, placement, projection) of every record of tests/golden/detectors.npz for a fixture scene.  The objective takes
+    every kind at every placement.  The numeric scene (another section
+    count, sections from the numeric hit search) takes a cross-section: every kind behind the last surface, some elsewhere."""
+    out = []
+    for kind in DETECTOR_CLOSED + DETECTOR_NUMERIC:
+        if scene == "objective":
+            places = DETECTOR_PLACEMENTS if kind != "tilted_ill" else ["offaxis"]
+        else:
+            places = ["behind"] if kind != "tilted_ill" else []
+            places = places + (["between", "stop", "lateral"] if kind in ("ring", "slit", "conic_k2", "sphere_neg", "tilted", "tilted_steep")
+                                   else [])
+        for pl in places:
+            for proj in (SPHERE_PROJECTIONS if kind.startswith("sphere") else [None]):
+                if scene == "numeric" and proj not in (None, "Equidistant", "Orthographic"):
+                    continue
+                out.append((kind, pl, proj))
+    return out
+
+
 SCENES2 = {  # SURVEY 8f rank 4 surfaces; kept apart from SCENES so that the seeds of the older fixtures stay put
     "prism": (prism_scene, 2000),
     "freeform": (freeform_scene, 2500),

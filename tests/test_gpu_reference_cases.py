@@ -102,39 +102,14 @@ def test_ill_conditioned_detector_hits_are_counted():
         RT.detector_spectrum()
 
 
-def front_focal_distance(surfaces, wl=555.):
-    """Paraxial distance of the front focal point in front of the first vertex.  surfaces: (R or inf, index behind the surface,
-    distance to the next vertex); the system stands in air."""
-    M = np.eye(2)
-    n_before = 1.0
-    for R, n_after, gap in surfaces:
-        power = 0.0 if np.isinf(R) else (n_after - n_before) / R
-        M = np.array([[1, 0], [-power / n_after, n_before / n_after]]) @ M
-        M = np.array([[1, gap], [0, 1]]) @ M
-        n_before = n_after
-    return -M[1, 1] / M[1, 0]  # a ray (s t, t) at the first vertex leaves with angle t (C s + D) = 0
-
-
 def test_detectors_of_every_kind_around_and_inside_an_objective():
     """tests/test_tracer_special.py:459-526 (test_hit_dector_many_surfaces_different_detector_surfaces): a strongly tilted
     detector that cuts through all four surfaces of a doublet (the hit lies in different sections for different rays), then a
     ring, a disc and a conic detector inside its second lens.  (The glasses of the reference's preset catalogue are stood in for by Abbe
     models of their n_d / V_d; the object is a synthetic picture.)"""
     with ot.global_options.no_warnings():
-        RT = ot.Raytracer(outline=[-10, 10, -10, 10, -10, 300])
-        RS = ot.RaySource(ot.RGBImage(scenes.synthetic_rgb_image(), [0.2, 0.2]), divergence="Lambertian", pos=[0, 0, 0],
-                          s=[0, 0, 1], div_angle=27)
-        RT.add(RS)
-        flint, crown = ot.RefractionIndex("Abbe", n=1.72825, V=28.41), ot.RefractionIndex("Abbe", n=1.713, V=53.83)
-        R1, R2 = 7.74, -7.29
-        s = front_focal_distance([(np.inf, float(flint(555.)), 0.5), (-R2, float(flint(555.)), 0.0001),
-                                  (-R2, float(crown(555.)), 5.3), (-R1, 1.0, 0.0)])
-        z1 = 0.6 + s + 0.5  # the front focal point 0.6 mm behind the object
-        L01 = ot.Lens(ot.CircularSurface(r=5.5), ot.SphericalSurface(r=5.5, R=-R2), d1=0.5, d2=0, pos=[0, 0, z1], n=flint, n2=flint)
-        L02 = ot.Lens(ot.SphericalSurface(r=5.5, R=-R2), ot.ConicSurface(r=5.5, R=-R1, k=-0.55), d1=0, d2=5.3,
-                      pos=[0, 0, z1 + 0.0001], n=crown)
-        RT.add(L01)
-        RT.add(L02)
+        RT = scenes.objective(ot)
+        L01, L02 = RT.lenses
         z_mid = 0.5 * (L01.extent[4] + L02.extent[5])
         det = ot.Detector(ot.TiltedSurface(r=3.5, normal=[2, 0, 1]), pos=[0, 0, z_mid])
         RT.add(det)
