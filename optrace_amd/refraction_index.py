@@ -113,6 +113,11 @@ class RefractionIndex(Spectrum):
                                    f" [{lo}, {hi}] for this material.")
         if kind == "Function":
             ns = np.asarray(self.func(x, **self.func_args), dtype=np.float64)
+        elif not np.array_equal(x.astype(np.float32), x):
+            # the kernel takes the float32 wavelengths rays carry; a wavelength that float32 cannot hold (a spectral line
+            # given as a double, in a lens design calculation) would be rounded by up to 3e-5 nm, 1e-9 in n: such calls are
+            # set-up arithmetic and get the float64 formulas of the paraxial analysis
+            ns = _host_index(self, x)
         else:
             pool: list = []
             medium = self._desc(pool)
@@ -210,15 +215,11 @@ _HOST_FORMULAS = {
 }
 
 
-def index_at(medium: RefractionIndex, wl: float) -> float:
-    """n of `medium` at one wavelength [nm], in float64 on the host, with the errors of `RefractionIndex.__call__`."""
-    x = np.asarray_chkfinite(wl, dtype=np.float64)
+def _host_index(medium: RefractionIndex, x: np.ndarray) -> np.ndarray:
+    """n of `medium` at the wavelengths `x` [nm] (float64 array of any shape), in float64 on the host; no range checks."""
     kind = medium.spectrum_type
     w = (x * 1e-3) ** 2
     if kind in ("Constant", "Function", "Data"):
-        if kind == "Data" and not medium._wls[0] <= x <= medium._wls[-1]:
-            raise RuntimeError(f"Wavelength range [{float(x):.5g}, {float(x):.5g}] larger than data range"
-                               f" [{medium._wls[0]}, {medium._wls[-1]}] for this material.")
         n = Spectrum._eval_host(medium, x)
     elif kind == "Abbe":
         if medium.V is None:
@@ -230,6 +231,16 @@ def index_at(medium: RefractionIndex, wl: float) -> float:
             raise TypeError(f"coefficient variable 'coeff' needs to be provided for n_type='{kind}'.")
         c, um = medium.coeff, x * 1e-3
         n = c[0] + c[1] / um + c[2] / um ** 3.5 if kind == "Conrady" else _HOST_FORMULAS[kind](c, w)
+    return np.array(n, dtype=np.float64)
+
+
+def index_at(medium: RefractionIndex, wl: float) -> float:
+    """n of `medium` at one wavelength [nm], in float64 on the host, with the errors of `RefractionIndex.__call__`."""
+    x = np.asarray_chkfinite(wl, dtype=np.float64)
+    if medium.spectrum_type == "Data" and not medium._wls[0] <= x <= medium._wls[-1]:
+        raise RuntimeError(f"Wavelength range [{float(x):.5g}, {float(x):.5g}] larger than data range"
+                           f" [{medium._wls[0]}, {medium._wls[-1]}] for this material.")
+    n = _host_index(medium, x)
     n = float(n)
     if n < 1:
         raise RuntimeError(f"Refraction index below 1 with value {n:.4g} at {float(x):.4g}nm.")
