@@ -39,7 +39,7 @@ PROJECTIONS = {None: PROJ_NONE, "Equidistant": PROJ_EQUIDISTANT, "Orthographic":
                "Equal-Area": PROJ_EQUAL_AREA, "Stereographic": PROJ_STEREOGRAPHIC}
 
 
-# The one routing rule of the detector stage (ot_api.hip numeric_hit / fused_ok, the same definition): the fused kernels serve
+# The one routing rule of the detector stage (ot_detect_api.hip numeric_hit / fused_ok, the same definition): the fused kernels serve
 # detectors with a closed-form hit (flat or conic) and no sphere projection with transcendentals.
 def numeric_hit(surf) -> bool:
     """The detector's hit needs the numeric search (aspheric, tilted, spline surfaces)."""

@@ -2,30 +2,10 @@
 // Reference: Raytracer._hit_detector raytracer.py:881-1051, SphericalSurface.sphere_projection
 // spherical_surface.py:36-97, RenderImage.render render_image.py:361-421 (+ misc.binning_indices_2d
 // misc.py:59-91, color.x/y/z_observer observers.py:14-41).
+// Defines kernels that are no templates: included by ot_detect_api.hip alone (and by the headers of that unit).
 #pragma once
 #include "ot_device.hpp"
 #include "cie_observer_table.inc"
-
-// ---- double min / max atomics (no native f64 min/max on global memory: CAS loop, one lane per wave) -------
-OT_DEV void atomic_min_f64(double* addr, double v) {
-    unsigned long long* a = (unsigned long long*)addr;
-    unsigned long long old = *a;
-    while (v < __longlong_as_double((long long)old)) {
-        unsigned long long assumed = old;
-        old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
-        if (old == assumed) break;
-    }
-}
-
-OT_DEV void atomic_max_f64(double* addr, double v) {
-    unsigned long long* a = (unsigned long long*)addr;
-    unsigned long long old = *a;
-    while (v > __longlong_as_double((long long)old)) {
-        unsigned long long assumed = old;
-        old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
-        if (old == assumed) break;
-    }
-}
 
 // Order-preserving map double -> uint64 (and back): min / max of doubles become single hardware integer atomics
 // (global_atomic_umin_x2 / umax_x2) instead of compare-and-swap loops on a plain, possibly stale, load.
@@ -63,19 +43,7 @@ __global__ void extent_final_kernel(const unsigned long long* __restrict__ slots
     extent4[c] = v;
 }
 
-OT_DEV double wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
-
-OT_DEV double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
-// Sum over the wave, delivered in lane 63 (row-wise DPP steps: no LDS traffic, unlike the shuffles above).
+// Sum over the wave, delivered in lane 63 (row-wise DPP steps: no LDS traffic, unlike the shuffles of wave_min / wave_max).
 #define OT_DPP_ADD(x, CTRL, ROWS)                                                                  \
     do {                                                                                           \
         const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROWS, 0xF, false); \
@@ -156,15 +124,6 @@ __global__ __launch_bounds__(256) void projection_kernel(double x0, double y0, d
     out[i] = v.x;
     out[i + n] = v.y;
     out[i + 2 * n] = v.z;
-}
-
-// direction of section k re-derived from the stored positions (RayStorage.rays_by_mask ray_storage.py:274-279)
-OT_DEV V3 section_dir(const ot_rays& R, int64_t r, int k) {
-    const int64_t N = R.N, nt = R.nt;
-    int k1 = (k < R.nt - 1) ? k + 1 : k;
-    V3 d = {R.p[r + N * k1] - R.p[r + N * k], R.p[r + N * (k1 + nt)] - R.p[r + N * (k + nt)],
-            R.p[r + N * (k1 + 2 * nt)] - R.p[r + N * (k + 2 * nt)]};
-    return normalize3(d);
 }
 
 struct Crop {
@@ -570,7 +529,7 @@ OT_DEV void observer_xyz_at(const double* obs, double l, double& xo, double& yo,
     }
 }
 
-// The same from the table of (value, difference) pairs (detector_setup in ot_api.hip: 471 x 6 behind the 471 x 3), for the kernels
+// The same from the table of (value, difference) pairs (detector_setup in ot_detect_api.hip: 471 x 6 behind the 471 x 3), for the kernels
 // that look a wavelength up per RECORD out of LDS: the three pairs of a row are 48 contiguous, 16-byte aligned bytes -- three
 // 16-byte LDS reads instead of six 8-byte ones with a 24-byte row stride -- and the difference np.interp forms per call
 // ((f[j + 1] - f[j]) / 1.0, the same f64 subtraction) comes ready: identical bits.

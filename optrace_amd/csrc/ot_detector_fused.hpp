@@ -15,6 +15,8 @@
 //   accum    per tile: ds_add_f64 of its chunks' records into the LDS tile, slabs, reduce        reads 12 B
 //
 // 80 B per ray and detector instead of 140, and 56 + 24 * n for n detector positions instead of 52 + 88 * n.
+//
+// Defines kernels that are no templates: included by ot_detect_api.hip alone (detector_setup takes their address).
 #pragma once
 #include <type_traits>
 #include "ot_render_tiles.hpp"
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(OT_FUSE_PROBE_WG) void fuse_probe_kernel(ot_rays R,
 
 // ---- direct path: detectors whose hits fall into few pixels -------------------------------------------------
 // render_kernel (ot_detector.hpp) with the hit search in front; the LDS hash is shared by the detectors of the launch
-// (key = pixel * 8 + detector).  Flat / conic detectors without a sphere projection only (fused_ok in ot_api.hip): no
+// (key = pixel * 8 + detector).  Flat / conic detectors without a sphere projection only (fused_ok in ot_detect_api.hip): no
 // Illinois loop, no spline code, no projection polynomials.
 template <int NDET>
 __global__ __launch_bounds__(1024) void fuse_direct_kernel(ot_rays R, int64_t first, int64_t count,

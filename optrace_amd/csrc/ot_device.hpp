@@ -892,3 +892,46 @@ OT_DEV void philox_normal2(uint64_t seed, uint64_t idx, uint32_t stream, uint32_
     z0 = r * cs;
     z1 = r * sn;
 }
+
+// ---- helpers shared by the stages behind the trace (detector, spectrum, image, focus) ------------------------
+// double min / max atomics (no native f64 min/max on global memory: CAS loop, one lane per wave)
+OT_DEV void atomic_min_f64(double* addr, double v) {
+    unsigned long long* a = (unsigned long long*)addr;
+    unsigned long long old = *a;
+    while (v < __longlong_as_double((long long)old)) {
+        unsigned long long assumed = old;
+        old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
+        if (old == assumed) break;
+    }
+}
+
+OT_DEV void atomic_max_f64(double* addr, double v) {
+    unsigned long long* a = (unsigned long long*)addr;
+    unsigned long long old = *a;
+    while (v > __longlong_as_double((long long)old)) {
+        unsigned long long assumed = old;
+        old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
+        if (old == assumed) break;
+    }
+}
+
+OT_DEV double wave_min(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+
+OT_DEV double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+// direction of section k re-derived from the stored positions (RayStorage.rays_by_mask ray_storage.py:274-279)
+OT_DEV V3 section_dir(const ot_rays& R, int64_t r, int k) {
+    const int64_t N = R.N, nt = R.nt;
+    int k1 = (k < R.nt - 1) ? k + 1 : k;
+    V3 d = {R.p[r + N * k1] - R.p[r + N * k], R.p[r + N * (k1 + nt)] - R.p[r + N * (k + nt)],
+            R.p[r + N * (k1 + 2 * nt)] - R.p[r + N * (k + 2 * nt)]};
+    return normalize3(d);
+}

@@ -8,8 +8,9 @@
 //
 // Rays are dense: w < 0 marks a ray that is not part of the search (already absorbed in front of the region).
 // Rays with w == 0 stay in: the reference counts them for the pixel number and the image extent.
+//
+// Defines kernels that are no templates: included by ot_image_api.hip alone.
 #pragma once
-#include "ot_detector.hpp"
 #include "ot_device.hpp"
 
 // workspace slots (doubles)

@@ -1,0 +1,81 @@
+// Host plumbing shared by the translation units of the C-ABI (ot_api.hip and ot_*_api.hip, one per stage): error reporting,
+// launch shapes, the scratch pool's front door, surface compilation and the source ranges.  Functions are declared here and
+// defined once, in the unit named beside them.  All of them are internal to the library: hidden visibility, so that the
+// dynamic symbol table holds the C-ABI and the trace launchers as before.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "ot_scene.hpp"
+#include "ot_scratch.hpp"
+
+#define OT_INTERNAL __attribute__((visibility("hidden")))
+
+// ---- errors (ot_api.hip: the one thread-local message behind ot_last_error) -----------------------------------------
+OT_INTERNAL int fail(int code, const std::string& msg);
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(OT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+    } while (0)
+
+OT_INTERNAL int require_device();  // ot_api.hip
+
+// ---- launch shapes and scratch layout -------------------------------------------------------------------------------
+static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+static inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// scratch layout: consecutive arrays, each on a 256-byte boundary
+struct Carver {
+    size_t off;
+    size_t operator()(size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes);
+        return o;
+    }
+};
+
+OT_INTERNAL int cu_count();  // ot_api.hip
+
+// ---- scratch pool (ot_api.hip, ot_scratch.hpp) ----------------------------------------------------------------------
+enum { OT_WS_RENDER = 0, OT_WS_FUSED = 1, OT_WS_FUSED_HITS = 2, OT_WS_AUTO = 3, OT_WS_DET = 4 };
+
+// -> lease on a block of at least `bytes` for this device, stream and purpose; empty when out of memory (the callers fall
+// back to paths without scratch)
+OT_INTERNAL ot_scratch::Lease workspace(int purpose, size_t bytes, hipStream_t st);
+
+// ---- surface compilation (ot_scene_api.hip) -------------------------------------------------------------------------
+OT_INTERNAL int compile_surface(const ot_surface& s, SurfDev& d);
+
+// What goes into the device table of a compiled surface (d.tab != nullptr): the caller's spline tables as they are; for
+// an asphere with more than OT_MAX_ASPH coefficients the layout of ot_device.hpp::asph_poly_long, built here:
+// a[npad] | d[npad], d_j = a_j (2j + 2) as in SurfDev::dcoeff, zeros behind the last coefficient.
+struct OT_INTERNAL DeviceTable {
+    std::vector<double> own;
+    const double* src = nullptr;
+    size_t len = 0;
+    DeviceTable(const ot_surface& s, const SurfDev& d);
+};
+
+// A compiled surface for the leaf entry points: its table (if any) is uploaded for the duration of the call.
+struct OT_INTERNAL LeafSurface {
+    SurfDev d;
+    double* dev_tab = nullptr;
+    hipStream_t st = nullptr;
+    int init(const ot_surface* surf, hipStream_t stream);
+    ~LeafSurface();
+};
+
+// ---- source ranges (ot_sources_api.hip) -----------------------------------------------------------------------------
+struct RangeArgs;  // ot_trace_kernel.hpp
+
+OT_INTERNAL void drop_range_cache(ot_sources* s);
+
+// Fills the kernel argument block; with more than OT_MAX_RANGES ranges the records go to device memory (kept in
+// the source table's cache until a different list arrives).
+OT_INTERNAL int make_ranges(const ot_source_range* ranges, int32_t n_ranges, const ot_sources* src_c, int64_t N,
+                            const RangeArgs** out);

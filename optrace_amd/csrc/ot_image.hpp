@@ -3,8 +3,9 @@
 // color.xyz_to_xyY xyz.py, the chroma clipping helper _triangle_intersect srgb.py:133-183 and _get_chroma_scale
 // srgb.py:186-222.  One lane per (down-binned) pixel; the few image-wide quantities (maxima, any-flags, the
 // minimum chroma factor) are reduced on the device between the passes (wave shuffle + one atomic per wave).
+// Defines kernels that are no templates: included by ot_image_api.hip alone.
 #pragma once
-#include "ot_detector.hpp"
+#include "ot_device.hpp"
 
 #define OT_IMG_IRRADIANCE 0
 #define OT_IMG_ILLUMINANCE 1

@@ -17,6 +17,8 @@
 //   reduce   slabs of a tile summed into the image, every pixel owned by one thread
 //
 // 68 B of traffic per hit instead of 4 contended atomics.  Sums are the same values added in another order.
+//
+// Defines kernels that are no templates: included by ot_detect_api.hip alone (detector_setup takes their address).
 #pragma once
 #include "ot_detector.hpp"
 

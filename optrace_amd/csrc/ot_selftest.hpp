@@ -4,6 +4,7 @@
 // through the core and through the compiler's own IEEE sequence (the same translation unit, -ffp-contract=off), the
 // result bits are compared, mismatches are counted and the first one is kept.
 // Driven by tests/test_gpu_arith_exact.py through ot_selftest_arith / ot_selftest_eval.
+// Defines kernels that are no templates: included by ot_api.hip alone.
 #pragma once
 #include "ot_device.hpp"
 

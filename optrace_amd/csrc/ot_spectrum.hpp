@@ -4,6 +4,7 @@
 // (bin_type = result_type(first, last, a)); the kernels below follow that arithmetic so that a ray lands in the
 // same bin.  Rays are given dense (weight 0 = not selected), as ot_detector_hits leaves them, or as a compact list
 // (`fill`: 1024 pieces of hit_piece_len(n) entries, piece k holding fill[k] entries at its front, ot_detector_req.fill).
+// Defines kernels that are no templates: included by ot_detect_api.hip alone (detector_setup takes their address).
 #pragma once
 #include "ot_detector.hpp"
 #include "ot_device.hpp"

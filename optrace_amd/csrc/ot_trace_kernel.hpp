@@ -1,7 +1,7 @@
 // The tracing kernel and its launch plumbing, shared by the translation units that instantiate its variants.
 //
 // One translation unit per feature level (ot_trace_f<level>.hip) instantiates the 10 variants of that level
-// (polarisation x generation x spectrum handling); ot_api.hip only calls launch_trace_feat<level>().  The split is a
+// (polarisation x generation x spectrum handling); ot_trace_api.hip only calls launch_trace_feat<level>().  The split is a
 // build-time matter (the variants compile in parallel, one level rebuilds alone) and changes nothing in the kernels.
 #pragma once
 #include "ot_trace.hpp"
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ke
 // for its living rays into a compact two-section ray storage (`TailOut`: the layout of ot_rays with nt = 2), which the
 // detector kernels read like any other storage.  C4 (2 surfaces, no_pol): 20 B per traced ray instead of 172 B written, and
 // the detector passes read 20 B instead of 56 B per traced ray.
-// Compaction as for the compact hit lists (ot_api.hip::ot_detector_hits_multi): wave k takes `cnt` slots of piece k mod 1024
+// Compaction as for the compact hit lists (ot_detect_api.hip::ot_detector_hits_multi): wave k takes `cnt` slots of piece k mod 1024
 // with ONE returning atomic on that piece's fill count (waves in flight spread over all counters).  The pieces are
 // interleaved in rows of 64 entries -- slot q of piece p lives at ((q >> 6) * 1024 + p) * 64 + (q & 63) -- and fill at the same
 // rate, so the storage is dense up to the fullest piece's row; tail_seal_kernel clears the ragged end (weight 0) and reports

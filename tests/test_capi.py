@@ -140,3 +140,44 @@ def test_tail_append_checks_its_arguments_before_anything_else():
     # 1024 pieces of 64 slots hold 1024 waves: one wave more (before + appended) does not fit 65536 slots
     assert call(storage(70000, 4), 0, 64, 1.0, 65536, tail) == -1 and b"smaller than" in lib.ot_last_error()
     assert call(rays, 0, 10, 1.0, 0, storage(65537, 2)) == -1
+
+
+def test_last_error_is_shared_by_every_unit():
+    """The C-ABI is one translation unit per stage (csrc/ot_api.hip, ot_*_api.hip); the message behind `ot_last_error` has
+    one definition for all of them (ot_host.hpp::fail).  One entry point of each unit, with an argument it refuses before any
+    device call: the return code, and that call's own message in `ot_last_error`.  The message is per thread."""
+    import threading
+
+    lib = _capi.load_library()
+    st = C.c_void_p()
+    out = C.c_void_p()
+    rays, req = _capi.Rays(), _capi.DetectorReq()
+    msgs = (C.c_int64 * 8)()
+    INVALID = -1  # OT_ERR_INVALID
+    calls = [  # (unit, call, its message)
+        ("ot_scene_api", lambda: lib.ot_scene_create(None, C.byref(out)), b"ot_scene_create: null argument"),
+        ("ot_sources_api", lambda: lib.ot_sources_create(None, 1, C.byref(out)), b"ot_sources_create: bad argument"),
+        ("ot_trace_api", lambda: lib.ot_trace(None, C.byref(rays), None, 0, msgs, st), b"ot_trace: null argument"),
+        ("ot_leaf_api", lambda: lib.ot_surface_mask(None, 0, None, None, None, st), b"ot_surface_mask: bad argument"),
+        ("ot_detect_api", lambda: lib.ot_detector_hits_multi(C.byref(rays), 0, 0, C.byref(req), 0, st),
+         b"ot_detector_hits: null argument"),
+        ("ot_image_api", lambda: lib.ot_image_convert(None, 4, 4, 1, 0, 1.0, 1.0, 0.0, float("nan"), msgs, msgs, st),
+         b"ot_image_convert: bad argument"),
+        ("ot_api", lambda: lib.ot_scratch_set_cap(-1), b"ot_scratch_set_cap: negative cap"),
+    ]
+    for unit, call, message in calls:
+        assert call() == INVALID, unit
+        assert message in lib.ot_last_error(), (unit, lib.ot_last_error())
+    # a second thread sees its own message, and this one keeps the last of its own
+    seen = {}
+
+    def other():
+        seen["before"] = lib.ot_last_error()
+        seen["rc"] = lib.ot_scene_create(None, C.byref(C.c_void_p()))
+        seen["after"] = lib.ot_last_error()
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen["rc"] == INVALID and seen["before"] == b"" and b"ot_scene_create: null argument" in seen["after"]
+    assert b"ot_scratch_set_cap: negative cap" in lib.ot_last_error()

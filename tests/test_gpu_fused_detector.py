@@ -229,7 +229,7 @@ def test_compact_hit_list_on_a_point_image_and_without_hits():
 
 
 def test_kept_scratch_grows_and_can_be_handed_back():
-    """The binning paths keep their scratch per stream between calls (csrc/ot_api.hip::workspace): a larger bundle after a
+    """The binning paths keep their scratch per stream between calls (csrc/ot_api.hip::workspace, declared in ot_host.hpp): a larger bundle after a
     smaller one reallocates, `ot_scratch_trim` returns everything to the driver, and the images do not depend on any of it."""
     from optrace_amd import _capi
     lib = _capi.load_library()

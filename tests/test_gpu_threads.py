@@ -1,5 +1,5 @@
 """The detector stage from two host threads at once.  Its one-time device set-up (dynamic-LDS limits of the binning kernels,
-the CIE observer table) is one record per device for the whole process (csrc/ot_api.hip `detector_setup`), shared by every
+the CIE observer table) is one record per device for the whole process (csrc/ot_detect_api.hip `detector_setup`), shared by every
 thread.  Each thread traces its own seeded Raytracer and renders an image with a user extent (`ot_detector_images`) and
 one with the one-pass automatic extent (`ot_detector_image_auto_*`); the results equal the same calls made in one thread."""
 import threading
