@@ -400,6 +400,18 @@ int ot_tail_append(const ot_rays* rays, int64_t first, int64_t count, double wei
 int ot_scene_set_timing(ot_scene* scene, int32_t on);
 int ot_scene_last_trace_ms(const ot_scene* scene, double* ms);
 
+/* The plane rays->n holds, for every ray and section, the refractive index of the medium the section runs in: a function
+ * of the scene, the section and the ray's wavelength alone, whether the ray is alive or not (raytracer.py:305, 327-332).
+ * Nothing in this library reads it, and it is a sixth of what a trace writes.  ot_scene_set_index_store(scene, 0) makes
+ * every later trace of this scene leave the plane untouched (rays->n must still be a valid buffer); the default, 1,
+ * stores it with every trace as before.  ot_rays_fill_index writes n[:, section] of the rays [first, first + count) from
+ * rays->wl, with the device functions and the spectrum handling (formulas, tables, per-line tables) of this scene's
+ * last stored trace -- ot_trace, ot_generate_and_trace, ot_generate_and_trace_host; before any: the formulas --, so
+ * that the plane is bit for bit what that trace stores with the switch on.  rays->nt must be the scene's section
+ * count; only rays->N, nt, n and wl are used.  Asynchronous on `stream`. */
+int ot_scene_set_index_store(ot_scene* scene, int32_t on);
+int ot_rays_fill_index(const ot_scene* scene, const ot_rays* rays, int64_t first, int64_t count, void* stream);
+
 /* ---- leaf operators (public Surface / RefractionIndex methods) ---------------------------------- */
 /* Surface.find_hit (surface.py:307, conic_surface.py:126): p, s are (n,3) F-order device arrays;
  * outputs p_hit (n,3) F-order, is_hit (n) uint8, ill (n) uint8: bit 0 = ill-conditioned bracket

@@ -153,6 +153,8 @@ SIGNATURES = {
     "ot_tail_append": (C.c_int, [C.POINTER(Rays), i64, i64, C.c_double, i64, C.POINTER(Rays), vp, vp, vp]),
     "ot_scene_set_timing": (C.c_int, [vp, i32]),
     "ot_scene_last_trace_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "ot_scene_set_index_store": (C.c_int, [vp, i32]),
+    "ot_rays_fill_index": (C.c_int, [vp, C.POINTER(Rays), i64, i64, vp]),
     "ot_surface_find_hit": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp, vp, vp]),
     "ot_surface_normals": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp]),
     "ot_surface_mask": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp]),

@@ -110,6 +110,11 @@ struct ot_scene {
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
+    // ot_scene_set_index_store: off = the trace kernels leave the plane ot_rays.n unwritten (ot_rays_fill_index writes it)
+    bool index_store = true;
+    // SPEC of the last stored trace (0 formulas, 1 + tables, 2 per-line tables; -1: none yet): ot_rays_fill_index evaluates
+    // the indices the way that launch did
+    int index_spec = -1;
 };
 
 // ---- sources -------------------------------------------------------------------------------------------

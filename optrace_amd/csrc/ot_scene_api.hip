@@ -488,6 +488,14 @@ extern "C" int ot_scene_set_timing(ot_scene* sc, int32_t on) {
     return OT_OK;
 }
 
+// The index plane ot_rays.n is a function of (scene, section, wavelength) alone and nothing in the library reads it: a caller
+// who does not need it after every trace switches its stores off and writes it with ot_rays_fill_index when it is asked for.
+extern "C" int ot_scene_set_index_store(ot_scene* sc, int32_t on) {
+    if (!sc) return fail(OT_ERR_INVALID, "ot_scene_set_index_store: null scene");
+    sc->index_store = on != 0;
+    return OT_OK;
+}
+
 extern "C" int ot_scene_last_trace_ms(const ot_scene* sc, double* ms) {
     if (!sc || !ms) return fail(OT_ERR_INVALID, "ot_scene_last_trace_ms: null argument");
     if (!sc->ev_valid) return fail(OT_ERR_INVALID, "no timed trace launch on this scene (ot_scene_set_timing)");

@@ -322,7 +322,7 @@ OT_DEV void store_section(const ot_rays& R, uint32_t o8, uint32_t o4, int sec, c
     store_f64(R.p + N * (sec + nt), o8, p.y);
     store_f64(R.p + N * (sec + 2 * nt), o8, p.z);
     store_f32(R.w + N * sec, o4, w);
-    store_f64(R.n + N * sec, o8, n);
+    if (R.n) store_f64(R.n + N * sec, o8, n);  // (null: see store_section_next)
     if (POL) {
         store_f32(R.pol + N * sec, o4, px);
         store_f32(R.pol + N * (sec + nt), o4, py);
@@ -355,8 +355,15 @@ OT_DEV void store_section_next(PlaneBases& b, uint32_t o8, uint32_t o4, const V3
     store_f64(b.py, o8, p.y);
     store_f64(b.pz, o8, p.z);
     store_f32(b.w, o4, w);
-    store_f64(b.n, o8, n);
-    b.px += b.N, b.py += b.N, b.pz += b.N, b.n += b.N, b.w += b.N;
+    // The index plane is a function of (scene, section, wavelength) alone: with the scene's index store switched off
+    // (ot_scene_set_index_store) the launcher hands in a null base, the plane stays unwritten -- 8 of 52 B per section
+    // with polarisation -- and ot_rays_fill_index writes it when somebody reads it.  The base is a kernel argument: a
+    // scalar branch, the same for every wave of the launch.
+    if (b.n) {
+        store_f64(b.n, o8, n);
+        b.n += b.N;
+    }
+    b.px += b.N, b.py += b.N, b.pz += b.N, b.w += b.N;
     if (POL) {
         store_f32(b.qx, o4, px);
         store_f32(b.qy, o4, py);

@@ -139,6 +139,8 @@ static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const Range
     if (lines && lds_cnt + lds_lines + lds_patch > 65000) lines = false;
     const size_t lds = ((lds_cnt + (lines ? lds_lines : 0) + 7) / 8) * 8 + lds_patch;
     unsigned int* slots = sc->cnt_slots;
+    const int spec = lines ? 2 : (tab ? 1 : 0);
+    if (!tail) sc->index_spec = spec;  // what ot_rays_fill_index has to repeat
     if (sc->timing) HIP_TRY(hipEventRecord(sc->ev0, st));
     // lanes address their ray with 32-bit byte offsets: launches of at most 2^28 rays, base pointers advanced
     const int64_t chunk = 1ll << 28;
@@ -153,6 +155,7 @@ static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const Range
         if (!tail) {
             L.part.p += base; L.part.s += base; L.part.w += base; L.part.n += base; L.part.wl += base;
             if (L.part.pol) L.part.pol += base;
+            if (!sc->index_store) L.part.n = nullptr;  // the kernel skips the plane (ot_trace.hpp::store_section_next)
         }
         L.sd = sd;
         L.rg = &r;
@@ -162,7 +165,7 @@ static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const Range
         L.base = base;
         L.pol = pol;
         L.gen = src != nullptr;
-        L.spec = (src && lines) ? 2 : (tab ? 1 : 0);
+        L.spec = spec;
         if (tail) {  // the render-only form of the same feature level
             switch (feat) {
                 case OT_FEAT(OT_HIT_CLOSED, 0): launch_trace_tail_feat<OT_FEAT(OT_HIT_CLOSED, 0)>(L, *tail); break;
@@ -222,6 +225,70 @@ extern "C" int ot_generate_and_trace_host(const ot_scene* scene, const ot_source
     if (int rc = launch_trace(scene, src, rg, rays, nullptr, seed, nullptr, stream)) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     std::memcpy(msgs_host, scene->pin_msgs, sizeof(int64_t) * (size_t)(OT_N_INFOS * scene->h.nt + 1));
+    return OT_OK;
+}
+
+// The index plane n[section, ray] of a traced storage, written on its own.  trace_ray sets a ray's index for every lane,
+// alive or not, hit or not: section 0 carries the ambient medium, a refracting step (kind <= OT_STEP_IDEAL) the medium behind
+// it, every other step the index before it -- a function of (scene, section, wavelength) alone.  This kernel walks the same
+// steps with the same device functions the trace kernel of variant SPEC uses (medium_n<TAB>; SPEC 2: the rows of the
+// per-line table and the same comparison that finds a ray's line), so the plane is bit for bit what that trace stores when
+// the scene's index store is on.  One ray per lane, 32-bit lane offsets from a wave-uniform plane base that advances by one
+// plane per section; streaming stores (the plane is written once and not read here).
+template <int SPEC>
+__global__ __launch_bounds__(256) void fill_index_kernel(const SceneDev* __restrict__ scp, const float* __restrict__ wlp,
+                                                         double* __restrict__ plane, int64_t stride, uint32_t count) {
+    constexpr bool TAB = (SPEC == 1);
+    const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
+    if (local >= count) return;
+    auto& sc = *as_const(scp);
+    const auto steps = as_const(sc.steps);
+    const auto media = as_const(sc.media);
+    const auto pool = as_const(sc.pool);
+    const float wl = wlp[local];
+    const double* ltab = sc.line_tab;
+    int lj = 0;
+    if (SPEC == 2) {
+        for (int j = 1; j < sc.n_lines; j++)
+            if ((float)ltab[j] == wl) lj = j;
+    }
+    const double* lrow = ltab + OT_MAX_LINES + lj;  // row 0 of this lane's column (trace_ray)
+    double n_cur = (SPEC == 2) ? lrow[(3 * sc.n_steps) * OT_MAX_LINES] : medium_n<TAB>(media[sc.n0], pool, wl);
+    __builtin_nontemporal_store(n_cur, &plane[local]);
+    for (int i = 0; i < sc.n_steps; i++) {
+        auto& st = steps[i];
+        if (st.kind <= OT_STEP_IDEAL)
+            n_cur = (SPEC == 2) ? lrow[(3 * i + 0) * OT_MAX_LINES] : medium_n<TAB>(media[st.n_next], pool, wl);
+        plane += stride;
+        __builtin_nontemporal_store(n_cur, &plane[local]);
+    }
+}
+
+extern "C" int ot_rays_fill_index(const ot_scene* sc, const ot_rays* rays, int64_t first, int64_t count, void* stream) {
+    if (!sc || !rays) return fail(OT_ERR_INVALID, "ot_rays_fill_index: null argument");
+    if (rays->N < 0 || !rays->n || !rays->wl) return fail(OT_ERR_INVALID, "ot_rays_fill_index: the ray storage needs n and wl");
+    if (rays->nt != sc->h.nt || rays->nt != sc->h.n_steps + 1)
+        return fail(OT_ERR_INVALID, "ray storage has " + std::to_string(rays->nt) + " sections, the scene needs " +
+                                        std::to_string(sc->h.nt));
+    if (first < 0 || count < 0 || first + count > rays->N) return fail(OT_ERR_INVALID, "ot_rays_fill_index: range outside the storage");
+    if (int rc = require_device()) return rc;
+    // the variant of the scene's last stored trace; none yet: formulas, as a trace of rays handed in would take
+    int spec = sc->index_spec >= 0 ? sc->index_spec : (sc->needs_tables ? 1 : 0);
+    if (spec == 2 && sc->h.n_lines < 1) spec = sc->needs_tables ? 1 : 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t chunk = 1ll << 28;  // 32-bit lane offsets, as the trace launches
+    for (int64_t base = first; base < first + count; base += chunk) {
+        const uint32_t n = (uint32_t)std::min<int64_t>(chunk, first + count - base);
+        const float* wl = rays->wl + base;
+        double* plane = rays->n + base;
+        if (spec == 2)
+            hipLaunchKernelGGL(fill_index_kernel<2>, grid_for(n), dim3(256), 0, st, sc->d, wl, plane, rays->N, n);
+        else if (spec == 1)
+            hipLaunchKernelGGL(fill_index_kernel<1>, grid_for(n), dim3(256), 0, st, sc->d, wl, plane, rays->N, n);
+        else
+            hipLaunchKernelGGL(fill_index_kernel<0>, grid_for(n), dim3(256), 0, st, sc->d, wl, plane, rays->N, n);
+    }
+    HIP_TRY(hipGetLastError());
     return OT_OK;
 }
 

@@ -8,6 +8,7 @@ n_list (N, nt) f64, wl_list (N,) f32, pol_list (N, nt, 3) f32 -- but live in dev
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -112,6 +113,45 @@ class TailStorage:
         self._cap = self.N = self.alive = 0
 
 
+class SceneRef:
+    """Owner of one `ot_scene` handle: the scene is destroyed when the last holder lets go.  The tracer holds its current
+    scene; a storage whose index plane is still to be filled holds the scene that traced its rays."""
+
+    def __init__(self, handle: C.c_void_p) -> None:
+        self.handle = handle
+        self._lib = _capi.load_library()
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self._lib.ot_scene_destroy(self.handle)
+            self.handle = None
+
+
+class _DeviceBuffers(dict):
+    """name -> flat device tensor of a `RayStorage`.  A plain dict but for the key "n": the tracer's scenes leave the index
+    plane unwritten (`ot_scene_set_index_store`), so reading that entry first lets the storage fill it (`_ensure_index`)."""
+
+    __slots__ = ("_owner",)
+
+    def __init__(self, owner: "RayStorage", items: dict = ()) -> None:
+        super().__init__(items)
+        self._owner = weakref.ref(owner)  # (no cycle: the buffers go back to the allocator with the last reference)
+
+    def _touch(self, key) -> None:
+        if key == "n":
+            owner = self._owner()
+            if owner is not None:
+                owner._ensure_index()
+
+    def __getitem__(self, key):
+        self._touch(key)
+        return dict.__getitem__(self, key)
+
+    def get(self, key, default=None):
+        self._touch(key)
+        return dict.get(self, key, default)
+
+
 class RayStorage(BaseClass):
 
     _tracked = False  # a result container: filling it must not look like a scene change
@@ -134,8 +174,13 @@ class RayStorage(BaseClass):
         self._N = 0
         self._Np = 0      # plane stride of the device buffers (= _N unless padded, see PAD_FROM)
         self._nt = 0
-        self._dev = {}    # name -> torch tensor (flat, component-major)
+        self._dev = _DeviceBuffers(self)  # name -> torch tensor (flat, component-major)
         self._host = {}   # name -> cached read-only numpy view
+        # The index plane `_dev["n"]` is written when it is read: a trace leaves it alone and sets the mark, together with
+        # the scene that traced the rays and how many of them the plane holds (`_index_pending`, `_ensure_index`).
+        self._n_stale = False
+        self._n_scene = None
+        self._n_count = 0
         self._powers = []
         self._ranges = None   # ot_source_range array of the current split (`_source_ranges`)
         self._rays_c = None   # ot_rays of the current buffers
@@ -178,8 +223,9 @@ class RayStorage(BaseClass):
 
         N, nt = int(N), int(nt)
         if not _alloc:
-            d["_dev"], d["_rays_c"], d["_host"] = {}, None, {}
+            d["_dev"], d["_rays_c"], d["_host"] = _DeviceBuffers(self), None, {}
             d["_N"], d["_Np"], d["_nt"] = N, N, nt
+            d["_n_stale"], d["_n_scene"] = False, None
             return
         Np = -(-N // self.PAD_TO) * self.PAD_TO if N >= self.PAD_FROM else N
         old = self._dev
@@ -189,7 +235,8 @@ class RayStorage(BaseClass):
         if not reuse:
             # (a trace with the shape of the previous one writes into the same buffers: host views already handed
             # out are copies, and nothing on the device outlives the trace that produced it)
-            d["_dev"] = {}  # the previous storage goes back to the allocator before the new one is requested
+            d["_dev"] = _DeviceBuffers(self)  # the previous storage goes back to the allocator before the new one is requested
+            d["_n_stale"], d["_n_scene"] = True, None  # a fresh plane: nothing to fill it from until a trace says so
 
             def alloc() -> dict:
                 return {
@@ -200,7 +247,7 @@ class RayStorage(BaseClass):
                     "wl": torch.empty(Np, dtype=torch.float32, device=dev),
                     "pol": None if no_pol else torch.empty(3 * nt * Np, dtype=torch.float32, device=dev),
                 }
-            d["_dev"] = alloc_retry(alloc)  # (out of memory: the library's kept binning scratch goes back first)
+            d["_dev"] = _DeviceBuffers(self, alloc_retry(alloc))  # (out of memory: the library's kept binning scratch goes back first)
             d["_rays_c"] = None
         d["_N"], d["_Np"], d["_nt"] = N, Np, nt
         d["_host"] = {}
@@ -243,11 +290,29 @@ class RayStorage(BaseClass):
         d = self._dev
         r = _capi.Rays()
         r.N, r.nt = self._Np, self._nt  # the plane stride; how many rays there are, the ranges / counts of each call say
+        # (the address of the index plane, not its contents: read past the hook of `_dev`, no fill)
         r.p, r.s, r.w, r.n, r.wl = (d["p"].data_ptr(), d["s"].data_ptr(), d["w"].data_ptr(),
-                                    d["n"].data_ptr(), d["wl"].data_ptr())
+                                    dict.__getitem__(d, "n").data_ptr(), d["wl"].data_ptr())
         r.pol = d["pol"].data_ptr() if d["pol"] is not None else None
         self.__dict__["_rays_c"] = r
         return r
+
+    def _index_pending(self, scene: SceneRef, count: int) -> None:
+        """A trace of `scene` is about to write this storage and leaves the index plane alone: rays [0, count) of the
+        plane are to be filled from that scene when the plane is read."""
+        d = self.__dict__
+        d["_n_stale"], d["_n_scene"], d["_n_count"] = True, scene, int(count)
+
+    def _ensure_index(self) -> None:
+        """Fill the index plane if it is stale (`ot_rays_fill_index`, a streaming kernel on the current stream; no
+        synchronisation, no host copy).  Called by `_dev` whenever its entry "n" is read."""
+        scene = self._n_scene
+        if not self._n_stale or scene is None:
+            return
+        _capi.check(_capi.load_library().ot_rays_fill_index(scene.handle, C.byref(self._rays_struct()), 0, self._n_count,
+                                                            stream_ptr()))
+        d = self.__dict__  # (after the launch: a call that fails leaves the plane marked and its scene held)
+        d["_n_stale"], d["_n_scene"] = False, None
 
     # blocks below this size are not cut further (their share of the rays, and of the time, is negligible)
     _MIN_BLOCK = 1 << 16

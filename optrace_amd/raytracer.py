@@ -27,7 +27,7 @@ from .base import check_type
 from .geometry.elements import Group, Aperture, Detector
 from .geometry.surfaces import Surface, Point, Line, SphericalSurface, RingSurface, SlitSurface
 from .options import global_options
-from .ray_storage import RayStorage, TailStorage
+from .ray_storage import RayStorage, TailStorage, SceneRef
 from .refraction_index import RefractionIndex
 from .render_image import RenderImage
 from .spectrum import LightSpectrum
@@ -115,6 +115,7 @@ class Raytracer(Group):
         self._last_trace_snapshot = None     # tracing_snapshot() of the last trace
         self._scene = None
         self._scene_handle = None
+        self._scene_ref = None  # owner of `_scene_handle` (ray_storage.SceneRef), shared with a storage that still needs it
         self._scene_key = None
         self._checked_key = None
         self._rays_known_current = False
@@ -126,7 +127,7 @@ class Raytracer(Group):
         self._new_lock = True
 
     # bookkeeping of the tracer itself: writing these is not a scene change (base.mutation_epoch)
-    _INTERNAL = frozenset(("_msgs", "_last_trace_snapshot", "_scene", "_scene_handle", "_scene_key", "_checked_key",
+    _INTERNAL = frozenset(("_msgs", "_last_trace_snapshot", "_scene", "_scene_handle", "_scene_ref", "_scene_key", "_checked_key",
                            "_rays_known_current", "_source_cache", "geometry_error", "fault_pos", "_record",
                            "_msgs_host", "_kernel_ms_log", "_lock", "_new_lock",
                            "seed"))  # (the RNG seed is read at every trace and part of nothing that is compiled or checked)
@@ -278,7 +279,11 @@ class Raytracer(Group):
         self._check_media()
         handle = C.c_void_p()
         _capi.check(lib.ot_scene_create(C.byref(self._scene.desc), C.byref(handle)))
+        self._scene_ref = SceneRef(handle)
         self._scene_handle = handle
+        # Nothing reads the index plane on the way from a trace to an image, a spectrum or a focus: the kernels leave it
+        # unwritten (a sixth of a trace's bytes) and the storage fills it when `n_list` is asked for (RayStorage._ensure_index)
+        _capi.check(lib.ot_scene_set_index_store(handle, 0))
         self._scene_key = key
         return self._scene
 
@@ -296,8 +301,8 @@ class Raytracer(Group):
                 n(wl)
 
     def _release_scene(self) -> None:
-        if self._scene_handle is not None and self._scene_handle.value:
-            _capi.load_library().ot_scene_destroy(self._scene_handle)
+        # (destroyed with its last holder: a storage whose index plane is not filled yet keeps the scene that traced it)
+        self._scene_ref = None
         self._scene_handle = None
         self._scene_key = None
 
@@ -414,6 +419,7 @@ class Raytracer(Group):
                                                            C.c_void_p(mb_t.data_ptr()), msgs_h.ctypes.data, stream_ptr()))
                 _tail.N, _tail.alive, _tail.traced = int(mb[0]), int(mb[1]), N
             else:
+                rays_obj._index_pending(self._scene_ref, N)
                 _capi.check(lib.ot_generate_and_trace_host(self._scene_handle, tab.handle, rng_c, len(rng_c), seed,
                                                            C.byref(rays), msgs_h.ctypes.data, stream_ptr()))
         else:
@@ -425,6 +431,7 @@ class Raytracer(Group):
                     rows = np.pad(rows, ((0, 0), (0, rays_obj._Np - N)))
                 hn = torch.from_numpy(np.ascontiguousarray(rows).reshape(-1)).to(dev)
             msgs = torch.zeros(n_msgs, dtype=torch.int64, device=dev)
+            rays_obj._index_pending(self._scene_ref, rays_obj._Np)  # (ot_trace walks the whole stride)
             _capi.check(lib.ot_trace(self._scene_handle, C.byref(rays), ptr(hn), seed, ptr(msgs), stream_ptr()))
             msgs_h = msgs.cpu().numpy()  # (synchronises the stream)
 
