@@ -184,18 +184,24 @@ static int detector_setup(const double** table) {
             }
             d.table = t;
         }
-        HIP_TRY(hipFuncSetAttribute((const void*)tile_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_PROBE_LDS));
-        HIP_TRY(hipFuncSetAttribute((const void*)tile_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_ACCUM_LDS));
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_accum_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_ACCUM_LDS));
-        HIP_TRY(hipFuncSetAttribute((const void*)spec_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OT_ACCUM_LDS));
         // the one-detector tile kernels stage their records in LDS: with many tiles more than the 64 KB a kernel gets unasked
         const int most = 96 * 1024, lb = (int)fuse_lb_lds(OT_LB_MAXK);
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_kernel<1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_lb_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-        HIP_TRY(hipFuncSetAttribute((const void*)fuse_tiles_lb_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
+        const struct {
+            const void* kernel;
+            int bytes;
+        } dynamic_lds[] = {
+            {(const void*)tile_probe_kernel, OT_PROBE_LDS},
+            {(const void*)tile_accum_kernel, OT_ACCUM_LDS},
+            {(const void*)fuse_accum_multi_kernel, OT_ACCUM_LDS},
+            {(const void*)spec_accum_kernel, OT_ACCUM_LDS},
+            {(const void*)fuse_tiles_kernel<1, 1, false>, most},
+            {(const void*)fuse_tiles_kernel<1, 2, false>, most},
+            {(const void*)fuse_tiles_kernel<1, 1, true>, most},
+            {(const void*)fuse_tiles_kernel<1, 2, true>, most},
+            {(const void*)fuse_tiles_lb_kernel<false>, lb},
+            {(const void*)fuse_tiles_lb_kernel<true>, lb},
+        };
+        for (const auto& k : dynamic_lds) HIP_TRY(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
         d.done = true;
     }
     *table = d.table;
@@ -242,24 +248,14 @@ static int render_accumulate(int64_t n, const unsigned int* fill, const double* 
     const auto direct = [&](const int* spread) {
         hipLaunchKernelGGL(render_kernel, dim3((unsigned)blocks), dim3(1024), 0, st, n, px, py, w, wl, a, table, hist, spread, fill);
     };
-    const RenderPath pin = render_path();
-    if (pin.direct || (n < OT_TILE_MIN_HITS && !pin.tiles)) {
-        direct(nullptr);
-        HIP_TRY(hipGetLastError());
-        return OT_OK;
-    }
     // long lists: a probe decides on the device whether the direct kernel or the tile path bins them
     // (ot_render_tiles.hpp); both are enqueued, the one that is not needed returns at once
+    const RenderPath pin = render_path();
     TileArgs t;
     t.a = a;
     t.tx = (Nx + OT_TILE_W - 1) / OT_TILE_W;
     t.ty = (Ny + OT_TILE_W - 1) / OT_TILE_W;
     t.K = t.tx * t.ty;
-    if (t.K > OT_TILE_MAX) {  // no image of RenderImage is this large; stay on the direct path
-        direct(nullptr);
-        HIP_TRY(hipGetLastError());
-        return OT_OK;
-    }
     t.n = n;
     t.piece = fill ? hit_piece_len(n) : ((n + OT_TILE_PIECES - 1) / OT_TILE_PIECES + 1023) / 1024 * 1024;
     t.chunk = ((n + 1023) / 1024 + 1023) / 1024 * 1024;
@@ -273,10 +269,12 @@ static int render_accumulate(int64_t n, const unsigned int* fill, const double* 
     const size_t o_cstart = carve(sizeof(int) * (t.K + 1));
     const size_t o_rec = carve(sizeof(TileRec) * (size_t)n);
     const size_t o_slabs = carve(sizeof(double) * OT_TILE_PX * 4 * (size_t)t.max_chunks);
-    const ot_scratch::Lease lease = workspace(OT_WS_RENDER, carve.off, st);
+    // The direct kernel alone: pinned, a short list, more tiles than any image of RenderImage has, or no room for the hit
+    // records (12 B per hit; the direct kernel needs no scratch)
+    ot_scratch::Lease lease;
+    if (!pin.direct && (pin.tiles || n >= OT_TILE_MIN_HITS) && t.K <= OT_TILE_MAX) lease = workspace(OT_WS_RENDER, carve.off, st);
     char* ws = lease.p();
     if (!ws) {
-        // no room for the hit records (12 B per hit): the direct kernel needs no scratch
         direct(nullptr);
         HIP_TRY(hipGetLastError());
         return OT_OK;
@@ -350,9 +348,10 @@ static ot_rays rays_from(const ot_rays& rays, int64_t first) {
 // small_k: two rays per thread and sub-block (images of at most 1024 tiles: 10-bit tile numbers); linebuf: the line-buffer
 // kernel, one 1024-thread workgroup per CU.
 struct TilePool {
+    bool linebuf, small_k;
     unsigned n_wg;
     int64_t piece;
-    TilePool(int64_t count, bool linebuf, bool small_k, int cus) {
+    TilePool(int64_t count, bool linebuf_, bool small_k_, int cus) : linebuf(linebuf_), small_k(small_k_) {
         const int64_t brt = linebuf ? OT_LB_BR * OT_LB_RPT : OT_FUSE_BR * (small_k ? 2 : 1);
         n_wg = (unsigned)std::min<int64_t>((linebuf ? 1 : OT_FUSE_WG_PER_CU) * (int64_t)cus, (count + brt - 1) / brt);
         piece = ((count + n_wg - 1) / n_wg + brt - 1) / brt * brt;
@@ -391,30 +390,60 @@ struct IndexLayout {
     }
 };
 
-// the launches of ot_detector_images' first pass: the direct kernel, and the tile kernel where a detector has a pool
-struct FusedPass {
-    const ot_rays& rays;
-    int64_t first, count;
-    const FuseOne* dd;
-    int n_reqs, KT;
-    const double* table;
-    unsigned blocks;
-    const TilePool& tp;
-    hipStream_t st;
-    template <int NDET, int RPT, bool PAIR>
-    void launch() const {
-        hipLaunchKernelGGL((fuse_direct_kernel<NDET>), dim3(blocks), dim3(1024), 0, st, rays, first, count, dd, n_reqs, table);
-        if (KT)
-            hipLaunchKernelGGL((fuse_tiles_kernel<NDET, RPT, false, PAIR>), dim3(tp.n_wg), dim3(OT_FUSE_BR), fuse_tiles_lds(KT), st,
-                               rays_from(rays, first), (uint32_t)count, dd, n_reqs, KT, (uint32_t)tp.piece);
+// A detector's chunk pool of the first tile pass: chunk_tile, chunk_fill and the records of rec_size bytes (f.cap set)
+struct PoolLayout {
+    size_t o_ctile, o_cfill, o_rec;
+    PoolLayout() = default;
+    PoolLayout(Carver& carve, uint32_t cap, size_t rec_size) {
+        o_ctile = carve(sizeof(uint32_t) * cap);
+        o_cfill = carve(sizeof(uint32_t) * cap);
+        o_rec = carve(rec_size * (size_t)cap * OT_FUSE_CH);
     }
-    template <bool PAIR>
-    void launch_multi() const {  // (unused entries of the unrolled detector loop cost registers: the smallest NDET that fits)
-        if (n_reqs <= 2) launch<2, 1, PAIR>();
-        else if (n_reqs <= 4) launch<4, 1, PAIR>();
-        else launch<8, 1, PAIR>();
+    void point(FuseOne& f, char* ws) const {
+        f.chunk_tile = (uint32_t*)(ws + o_ctile);
+        f.chunk_fill = (uint32_t*)(ws + o_cfill);
+        f.rec = (TileRec*)(ws + o_rec);
     }
 };
+
+// what every fused launch knows of a detector: the surface, its crop and projection, and the tile grid of its image
+static void fuse_fill_detector(FuseOne& f, const LeafSurface& ls, const ot_surface* detector, const double* crop4, int32_t projection,
+                               int32_t tx, int32_t K, bool tiles_ok) {
+    std::memset(&f, 0, sizeof(f));
+    f.det = ls.d;
+    f.Rcurv = detector->R;
+    if (crop4) f.crop = {crop4[0], crop4[1], crop4[2], crop4[3], 1};
+    f.projection = projection;
+    f.tx = tx;
+    f.K = K;
+    f.tiles_ok = tiles_ok;
+}
+
+// The first tile pass over `count` rays from `first` on for n_det detectors with KT tiles in all.  One detector: line
+// buffers, else two rays per thread, else one (tp); several: the smallest NDET that fits (unused entries of the unrolled
+// detector loop cost registers), and PAIR where the storage has two sections (a tail storage): every hit from the prefetched
+// pair, no section search.  SPECX (the automatic extent) has one detector.
+template <bool SPECX>
+static void launch_tile_pass(const ot_rays& rays, int64_t first, int64_t count, const FuseOne* dd, int n_det, int KT, const TilePool& tp,
+                             hipStream_t st) {
+    const ot_rays part = rays_from(rays, first);
+#define OT_LAUNCH_TILES(ND, RPT, PAIR)                                                                                              \
+    hipLaunchKernelGGL((fuse_tiles_kernel<ND, RPT, SPECX, PAIR>), dim3(tp.n_wg), dim3(OT_FUSE_BR), fuse_tiles_lds(KT), st, part, \
+                       (uint32_t)count, dd, n_det, KT, (uint32_t)tp.piece)
+    if (tp.linebuf) {
+        hipLaunchKernelGGL(fuse_tiles_lb_kernel<SPECX>, dim3(tp.n_wg), dim3(OT_LB_BR), fuse_lb_lds(KT), st, part, (uint32_t)count, dd, KT,
+                           (uint32_t)tp.piece);
+    } else if (n_det == 1) {
+        if (tp.small_k) OT_LAUNCH_TILES(1, 2, false); else OT_LAUNCH_TILES(1, 1, false);
+    } else if constexpr (!SPECX) {
+        if (rays.nt == 2) {
+            if (n_det <= 2) OT_LAUNCH_TILES(2, 1, true); else if (n_det <= 4) OT_LAUNCH_TILES(4, 1, true); else OT_LAUNCH_TILES(8, 1, true);
+        } else {
+            if (n_det <= 2) OT_LAUNCH_TILES(2, 1, false); else if (n_det <= 4) OT_LAUNCH_TILES(4, 1, false); else OT_LAUNCH_TILES(8, 1, false);
+        }
+    }
+#undef OT_LAUNCH_TILES
+}
 
 extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t count, const ot_detector_image_req* reqs,
                                   int32_t n_reqs, void* stream) {
@@ -497,28 +526,21 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
     const size_t o_flags = carve(sizeof(int) * 4 * n_reqs);  // per detector: spread, -, overflow, pad
     const size_t o_pcnt = carve(sizeof(int) * 2 * n_reqs);   // probe: distinct pixels, workgroups done
     const size_t o_pset = carve(sizeof(int) * OT_TILE_PROBE_SET * (size_t)n_reqs);  // probe: pixel sets
-    std::vector<size_t> o_ctile(n_reqs), o_cfill(n_reqs), o_rec(n_reqs);
+    PoolLayout pools[OT_DET_MAX];
     for (int k = 0; k < n_reqs; k++) {
         FuseOne& f = host[k];
-        std::memset(&f, 0, sizeof(f));
         const ot_detector_image_req& q = reqs[k];
-        f.det = ls[k].d;
-        f.Rcurv = q.detector->R;
-        if (q.crop4) f.crop = {q.crop4[0], q.crop4[1], q.crop4[2], q.crop4[3], 1};
-        f.projection = q.projection;
+        const int K = tile_count(q.Nx, q.Ny);
+        fuse_fill_detector(f, ls[k], q.detector, q.crop4, q.projection, (q.Nx + OT_TILE_W - 1) / OT_TILE_W, K,
+                           want_tiles && K <= OT_TILE_MAX && K <= OT_FUSE_LDS_ENTRIES);
         f.a = render_args(q.extent, q.Nx, q.Ny, q.weight_scale);
-        f.tx = (q.Nx + OT_TILE_W - 1) / OT_TILE_W;
-        f.K = tile_count(q.Nx, q.Ny);
         f.ill = (unsigned long long*)q.ill_count;
         f.hist = q.hist;
-        f.tiles_ok = want_tiles && f.K <= OT_TILE_MAX && f.K <= OT_FUSE_LDS_ENTRIES;
         f.koff = KT;
         if (f.tiles_ok) {
             KT += f.K;
             tp.size(f);
-            o_ctile[k] = carve(sizeof(uint32_t) * f.cap);
-            o_cfill[k] = carve(sizeof(uint32_t) * f.cap);
-            o_rec[k] = carve(sizeof(TileRec) * (size_t)f.cap * OT_FUSE_CH);
+            pools[k] = PoolLayout(carve, f.cap, sizeof(TileRec));
             Kmax = std::max(Kmax, f.K);
             capmax = std::max(capmax, f.cap);
         }
@@ -544,11 +566,7 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
         FuseOne& f = host[k];
         f.spread = flags + 4 * k;
         f.overflow = flags + 4 * k + 2;
-        if (f.tiles_ok) {
-            f.chunk_tile = (uint32_t*)(ws + o_ctile[k]);
-            f.chunk_fill = (uint32_t*)(ws + o_cfill[k]);
-            f.rec = (TileRec*)(ws + o_rec[k]);
-        }
+        if (f.tiles_ok) pools[k].point(f, ws);
     }
     hipError_t err = hipMemsetAsync(flags, 0, sizeof(int) * 4 * n_reqs, st);
     if (err == hipSuccess) err = hipMemcpyAsync(ws + o_dets, host.data(), sizeof(FuseOne) * n_reqs, hipMemcpyHostToDevice, st);
@@ -569,19 +587,15 @@ extern "C" int ot_detector_images(const ot_rays* rays, int64_t first, int64_t co
                 hipLaunchKernelGGL(fuse_probe_kernel, pg, dim3(OT_FUSE_PROBE_WG), 0, st, *rays, first, count, dd, pset, pcnt);
             }
         }
-        const FusedPass pass{*rays, first, count, dd, n_reqs, KT, table, (unsigned)std::min<int64_t>(cus, (count + 1023) / 1024), tp, st};
-        if (linebuf) {
-            hipLaunchKernelGGL((fuse_direct_kernel<1>), dim3(pass.blocks), dim3(1024), 0, st, *rays, first, count, dd, n_reqs, table);
-            if (KT)
-                hipLaunchKernelGGL(fuse_tiles_lb_kernel<false>, dim3(tp.n_wg), dim3(OT_LB_BR), fuse_lb_lds(KT), st, rays_from(*rays, first),
-                                   (uint32_t)count, dd, KT, (uint32_t)tp.piece);
-        } else if (n_reqs == 1) {
-            if (small_k) pass.launch<1, 2, false>(); else pass.launch<1, 1, false>();
-        } else if (rays->nt == 2) {  // two sections (a tail storage): every hit from the prefetched pair, no section search
-            pass.launch_multi<true>();
-        } else {
-            pass.launch_multi<false>();
-        }
+        // the direct kernel (it returns at once for a detector whose verdict is "tiles"), and the tile pass where a detector has a pool
+        const dim3 dg((unsigned)std::min<int64_t>(cus, (count + 1023) / 1024));
+#define OT_LAUNCH_DIRECT(ND) hipLaunchKernelGGL((fuse_direct_kernel<ND>), dg, dim3(1024), 0, st, *rays, first, count, dd, n_reqs, table)
+        if (n_reqs == 1) OT_LAUNCH_DIRECT(1);
+        else if (n_reqs <= 2) OT_LAUNCH_DIRECT(2);
+        else if (n_reqs <= 4) OT_LAUNCH_DIRECT(4);
+        else OT_LAUNCH_DIRECT(8);
+#undef OT_LAUNCH_DIRECT
+        if (KT) launch_tile_pass<false>(*rays, first, count, dd, n_reqs, KT, tp, st);
         err = hipGetLastError();
         // tile path, all detectors per launch: chunks grouped by tile, LDS accumulation, slabs summed into the images
         if (err == hipSuccess && KT) {
@@ -639,13 +653,6 @@ static int auto_detector(const char* who, const ot_rays* rays, int64_t first, in
     return OT_OK;
 }
 
-static void auto_fill_detector(FuseOne& f, const LeafSurface& ls, const ot_surface* detector, int32_t projection) {
-    std::memset(&f, 0, sizeof(f));
-    f.det = ls.d;
-    f.Rcurv = detector->R;
-    f.projection = projection;
-}
-
 extern "C" int ot_detector_extent_sample(const ot_rays* rays, int64_t first, int64_t count, const ot_surface* detector,
                                          int32_t projection, int32_t stride, double* extent4, void* stream) {
     if (int rc = auto_detector("ot_detector_extent_sample", rays, first, count, detector, projection)) return rc;
@@ -659,7 +666,7 @@ extern "C" int ot_detector_extent_sample(const ot_rays* rays, int64_t first, int
     char* ws = lease.p();
     if (!ws) return fail(OT_ERR_HIP, "ot_detector_extent_sample: no scratch memory");
     FuseOne f;
-    auto_fill_detector(f, ls, detector, projection);
+    fuse_fill_detector(f, ls, detector, nullptr, projection, 0, 0, false);
     f.g.ext_slots = (unsigned long long*)(ws + h.o_slots);
     hipLaunchKernelGGL(put_kernel<FuseOne>, dim3(1), dim3(64), 0, st, f, (FuseOne*)(ws + h.o_dets));
     hipLaunchKernelGGL(extent_init_kernel, dim3(1), dim3(4 * OT_EXT_SLOTS), 0, st, f.g.ext_slots);
@@ -692,11 +699,7 @@ extern "C" int ot_detector_image_auto_begin(const ot_rays* rays, int64_t first, 
 
     std::unique_ptr<ot_auto_image> im(new ot_auto_image);
     FuseOne& f = im->f;
-    auto_fill_detector(f, ls, detector, projection);
-    f.tx = tiles[0];
-    f.K = (int32_t)K;
-    f.tiles_ok = 1;
-    f.koff = 0;
+    fuse_fill_detector(f, ls, detector, nullptr, projection, tiles[0], (int32_t)K, true);
     tp.size(f);
     f.g.X0 = origin[0];
     f.g.Y0 = origin[1];
@@ -710,9 +713,7 @@ extern "C" int ot_detector_image_auto_begin(const ot_rays* rays, int64_t first, 
 
     const AutoHead h;
     Carver carve{h.end};
-    const size_t o_ctile = carve(sizeof(uint32_t) * f.cap);
-    const size_t o_cfill = carve(sizeof(uint32_t) * f.cap);
-    const size_t o_rec = carve(sizeof(SpecRec) * (size_t)f.cap * OT_FUSE_CH);
+    const PoolLayout pool(carve, f.cap, sizeof(SpecRec));
     const size_t o_esc = carve(sizeof(SpecRec) * (size_t)f.g.esc_cap);
     im->idx = IndexLayout(carve, f.K, f.cap, 1);
     im->lease = workspace(OT_WS_AUTO, carve.off, st);
@@ -727,24 +728,12 @@ extern "C" int ot_detector_image_auto_begin(const ot_rays* rays, int64_t first, 
     f.overflow = flags + 2;
     f.g.esc_n = (unsigned int*)(flags + 3);
     f.g.ext_slots = (unsigned long long*)(ws + h.o_slots);
-    f.chunk_tile = (uint32_t*)(ws + o_ctile);
-    f.chunk_fill = (uint32_t*)(ws + o_cfill);
-    f.rec = (TileRec*)(ws + o_rec);
+    pool.point(f, ws);
     f.g.esc = (SpecRec*)(ws + o_esc);
     hipLaunchKernelGGL(put_kernel<int4>, dim3(1), dim3(64), 0, st, make_int4(1, 0, 0, 0), (int4*)flags);  // spread = 1: tiles always
     hipLaunchKernelGGL(put_kernel<FuseOne>, dim3(1), dim3(64), 0, st, f, (FuseOne*)(ws + h.o_dets));
     hipLaunchKernelGGL(extent_init_kernel, dim3(1), dim3(4 * OT_EXT_SLOTS), 0, st, f.g.ext_slots);
-    const ot_rays part = rays_from(*rays, first);
-    const FuseOne* dd = (const FuseOne*)(ws + h.o_dets);
-    if (linebuf)
-        hipLaunchKernelGGL(fuse_tiles_lb_kernel<true>, dim3(tp.n_wg), dim3(OT_LB_BR), fuse_lb_lds(f.K), st, part, (uint32_t)count, dd, f.K,
-                           (uint32_t)tp.piece);
-    else if (small_k)
-        hipLaunchKernelGGL((fuse_tiles_kernel<1, 2, true>), dim3(tp.n_wg), dim3(OT_FUSE_BR), fuse_tiles_lds(f.K), st, part, (uint32_t)count,
-                           dd, 1, f.K, (uint32_t)tp.piece);
-    else
-        hipLaunchKernelGGL((fuse_tiles_kernel<1, 1, true>), dim3(tp.n_wg), dim3(OT_FUSE_BR), fuse_tiles_lds(f.K), st, part, (uint32_t)count,
-                           dd, 1, f.K, (uint32_t)tp.piece);
+    launch_tile_pass<true>(*rays, first, count, (const FuseOne*)(ws + h.o_dets), 1, f.K, tp, st);
     hipLaunchKernelGGL(spec_result_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)f.g.ext_slots,
                        (const unsigned int*)f.g.esc_n, f.g.esc_cap, result6);
     HIP_TRY(hipGetLastError());

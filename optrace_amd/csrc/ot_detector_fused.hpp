@@ -217,11 +217,7 @@ __global__ __launch_bounds__(1024) void fuse_direct_kernel(ot_rays R, int64_t fi
                         break;
                     }
                 }
-                double* hv = (slot >= 0) ? &hval[slot * 4] : F.hist + (int64_t)(key / OT_DET_MAX) * 4;
-                unsafeAtomicAdd(hv + 0, a0);
-                unsafeAtomicAdd(hv + 1, a1);
-                unsafeAtomicAdd(hv + 2, a2);
-                unsafeAtomicAdd(hv + 3, a3);
+                add4((slot >= 0) ? &hval[slot * 4] : F.hist + (int64_t)(key / OT_DET_MAX) * 4, 1, a0, a1, a2, a3);
             });
         }
     }
@@ -766,7 +762,7 @@ struct FuseIndex {
 
 // chunks per tile: LDS histogram per workgroup (16 chunk numbers per thread), one global add per tile and workgroup
 #define OT_FUSE_IDX_PER 16
-OT_DEV void fuse_chunk_hist_body(const FuseOne& F, const FuseIndex& ix, const unsigned int bx, const unsigned int by) {
+OT_DEV void fuse_chunk_hist_body(const FuseOne& F, const FuseIndex& ix, const unsigned int bx) {
     if (!F.spread[0]) return;
     const unsigned int n = F.cap;
     const unsigned int c0 = bx * (1024 * OT_FUSE_IDX_PER);
@@ -786,14 +782,14 @@ OT_DEV void fuse_chunk_hist_body(const FuseOne& F, const FuseIndex& ix, const un
         if (h[i]) atomicAdd(&ix.tile_n[i], h[i]);
 }
 __global__ __launch_bounds__(1024) void fuse_chunk_hist_kernel(FuseOne F, FuseIndex ix) {
-    fuse_chunk_hist_body(F, ix, blockIdx.x, blockIdx.y);
+    fuse_chunk_hist_body(F, ix, blockIdx.x);
 }
 // several detectors in one launch (blockIdx.z), their records in device memory
 __global__ __launch_bounds__(1024) void fuse_chunk_hist_multi_kernel(const FuseOne* __restrict__ dets, const FuseIndex* __restrict__ ixs) {
-    fuse_chunk_hist_body(dets[blockIdx.z], ixs[blockIdx.z], blockIdx.x, blockIdx.y);
+    fuse_chunk_hist_body(dets[blockIdx.z], ixs[blockIdx.z], blockIdx.x);
 }
 
-OT_DEV void fuse_chunk_scan_body(const FuseOne& F, const FuseIndex& ix, const unsigned int bx, const unsigned int by) {
+OT_DEV void fuse_chunk_scan_body(const FuseOne& F, const FuseIndex& ix) {
     if (!F.spread[0]) return;
     // exclusive scans of the chunk counts (tstart) and of the workgroups they take (wstart) over K <= 2048 tiles: two
     // tiles per thread, wave scans by shuffles, the 16 wave totals through LDS
@@ -821,15 +817,15 @@ OT_DEV void fuse_chunk_scan_body(const FuseOne& F, const FuseIndex& ix, const un
     if (i1 < F.K) ix.tile_n[i1] = 0u;
 }
 __global__ __launch_bounds__(1024) void fuse_chunk_scan_kernel(FuseOne F, FuseIndex ix) {
-    fuse_chunk_scan_body(F, ix, blockIdx.x, blockIdx.y);
+    fuse_chunk_scan_body(F, ix);
 }
 // several detectors in one launch (blockIdx.z), their records in device memory
 __global__ __launch_bounds__(1024) void fuse_chunk_scan_multi_kernel(const FuseOne* __restrict__ dets, const FuseIndex* __restrict__ ixs) {
-    fuse_chunk_scan_body(dets[blockIdx.z], ixs[blockIdx.z], blockIdx.x, blockIdx.y);
+    fuse_chunk_scan_body(dets[blockIdx.z], ixs[blockIdx.z]);
 }
 
 // the workgroup's chunks of a tile get consecutive places behind one global reservation per tile
-OT_DEV void fuse_chunk_place_body(const FuseOne& F, const FuseIndex& ix, const unsigned int bx, const unsigned int by) {
+OT_DEV void fuse_chunk_place_body(const FuseOne& F, const FuseIndex& ix, const unsigned int bx) {
     if (!F.spread[0]) return;
     const unsigned int n = F.cap;
     const unsigned int c0 = bx * (1024 * OT_FUSE_IDX_PER);
@@ -857,19 +853,49 @@ OT_DEV void fuse_chunk_place_body(const FuseOne& F, const FuseIndex& ix, const u
         if (tl[k] != OT_FUSE_NONE) ix.list[h[tl[k]] + rank[k]] = c0 + k * 1024 + threadIdx.x;
 }
 __global__ __launch_bounds__(1024) void fuse_chunk_place_kernel(FuseOne F, FuseIndex ix) {
-    fuse_chunk_place_body(F, ix, blockIdx.x, blockIdx.y);
+    fuse_chunk_place_body(F, ix, blockIdx.x);
 }
 // several detectors in one launch (blockIdx.z), their records in device memory
 __global__ __launch_bounds__(1024) void fuse_chunk_place_multi_kernel(const FuseOne* __restrict__ dets, const FuseIndex* __restrict__ ixs) {
-    fuse_chunk_place_body(dets[blockIdx.z], ixs[blockIdx.z], blockIdx.x, blockIdx.y);
+    fuse_chunk_place_body(dets[blockIdx.z], ixs[blockIdx.z], blockIdx.x);
+}
+
+// One record into the LDS tile of the accumulation.  TileRec: its pixel inside the tile came with it.
+OT_DEV void fuse_accum_add(const FuseOne& F, const TileRec& rec, const double* obs, double* tile, int, int) {
+    const double wm = (double)rec.w * F.a.ws;
+    double xo, yo, zo;
+    observer_xyz_at6(obs, (double)rec.wl, xo, yo, zo);
+    add4_hit(tile + (int)rec.px, OT_TILE_PX, xo, yo, zo, wm);
+}
+// SpecRec (automatic extent, the last section of this file): the LDS tile is the window [ox, ox + 64) x [oy, oy + 64) of the
+// final image that covers provisional tile t, the record is binned with the exact rule, and one outside its window goes
+// straight to the image.
+OT_DEV void spec_origin(const FuseOne& F, int t, int& ox, int& oy) {
+    const int tcx = t % F.g.tx, tcy = t / F.g.tx;
+    // one pixel of slack: membership in a tile was decided by floor((x - X0) / tw), its corner here is X0 + tcx * tw
+    ox = (int)floor(F.a.fx * (F.g.X0 + (double)tcx * F.g.tw - F.a.x0)) - 1;
+    oy = (int)floor(F.a.fy * (F.g.Y0 + (double)tcy * F.g.th - F.a.y0)) - 1;
+}
+OT_DEV void fuse_accum_add(const FuseOne& F, const SpecRec& rec, const double* obs, double* tile, int ox, int oy) {
+    int32_t px, py;
+    const int pix = hit_pixel(F.a, rec.x, rec.y, px, py);
+    if (pix < 0) return;
+    const double wm = (double)rec.w * F.a.ws;
+    double xo, yo, zo;
+    observer_xyz_at6(obs, (double)rec.wl, xo, yo, zo);
+    const int lx = px - ox, ly = py - oy;
+    if ((unsigned)lx < (unsigned)OT_TILE_W && (unsigned)ly < (unsigned)OT_TILE_W)
+        add4_hit(tile + ((ly << 6) | lx), OT_TILE_PX, xo, yo, zo, wm);
+    else
+        add4_hit(F.hist + (int64_t)pix * 4, 1, xo, yo, zo, wm);
 }
 
 // Accumulation, one workgroup per OT_FUSE_CPW chunks of a tile (wstart): the hits of an image are rarely spread evenly
 // -- C4's picture covers a fifth of the detector, 42 of 225 tiles hold every record -- and a fixed number of workgroups
 // per tile left most CUs idle behind the few heavy tiles (1.7 of 4 waves per SIMD resident on average).  Workgroup b
-// finds its tile by bisection of wstart in LDS, adds its chunks into an LDS tile and writes slab b.
+// finds its tile by bisection of wstart in LDS, adds its chunks of REC records into an LDS tile and writes slab b.
+template <class REC>
 OT_DEV void fuse_accum_body(const FuseOne& F, const FuseIndex& ix, const double* __restrict__ table, const unsigned int bx, const unsigned int stride) {
-    if (!F.spread[0]) return;
     extern __shared__ double lds[];  // [TILE_PX * 4 tile] [471 * 6 observer table: (value, difference) pairs]; the tile part first holds wstart
     double* tile = lds;
     double* obs = lds + OT_TILE_PX * 4;
@@ -903,14 +929,16 @@ OT_DEV void fuse_accum_body(const FuseOne& F, const FuseIndex& ix, const double*
             s_fill[i] = F.chunk_fill[c];
         }
         __syncthreads();
+        int ox = 0, oy = 0;
+        if constexpr (std::is_same<REC, SpecRec>::value) spec_origin(F, t, ox, oy);
         // The workgroup's chunk numbers and fill counts go to LDS first (list -> fill -> record used to be three dependent
         // round trips per round), and the records of round i + 1 are requested before those of round i are added.
         constexpr int PER = 1024 / OT_FUSE_CH;  // chunks a workgroup handles at once
         constexpr int DEPTH = 4;                // chunk rounds per stage; two stages in flight per thread
         const int g = threadIdx.x / OT_FUSE_CH, slot = threadIdx.x % OT_FUSE_CH;
         const int n_c = (int)(j_end - j_begin);
-        const TileRec* __restrict__ recs = F.rec;
-        auto load = [&](int first, TileRec* rec, bool* ok) {
+        const REC* __restrict__ recs = (const REC*)F.rec;
+        auto load = [&](int first, REC* rec, bool* ok) {
     #pragma unroll
             for (int k = 0; k < DEPTH; k++) {
                 const int i = first + k * PER, ic = i < n_c ? i : 0;
@@ -918,23 +946,12 @@ OT_DEV void fuse_accum_body(const FuseOne& F, const FuseIndex& ix, const double*
                 if (ok[k]) rec[k] = recs[(size_t)s_chunk[ic] * OT_FUSE_CH + slot];
             }
         };
-        auto add = [&](const TileRec* rec, const bool* ok) {
+        auto add = [&](const REC* rec, const bool* ok) {
     #pragma unroll
-            for (int k = 0; k < DEPTH; k++) {
-                if (!ok[k]) continue;
-                const double wm = (double)rec[k].w * F.a.ws;
-                double xo, yo, zo;
-                observer_xyz_at6(obs, (double)rec[k].wl, xo, yo, zo);
-                // plane-major tile [channel][pixel]: the lanes of one add then spread over 16 bank pairs; pixel-major
-                // (4 doubles per pixel) would leave them 4 and make every add a 16-way bank conflict
-                double* hv = tile + (int)rec[k].px;
-                unsafeAtomicAdd(hv + 0 * OT_TILE_PX, xo * wm);
-                unsafeAtomicAdd(hv + 1 * OT_TILE_PX, yo * wm);
-                unsafeAtomicAdd(hv + 2 * OT_TILE_PX, zo * wm);
-                unsafeAtomicAdd(hv + 3 * OT_TILE_PX, 1.0 * wm);
-            }
+            for (int k = 0; k < DEPTH; k++)
+                if (ok[k]) fuse_accum_add(F, rec[k], obs, tile, ox, oy);
         };
-        TileRec ra[DEPTH], rb[DEPTH];
+        REC ra[DEPTH], rb[DEPTH];
         bool oa[DEPTH], ob[DEPTH];
         load(g, ra, oa);
         for (int i0 = g; i0 < n_c; i0 += 2 * PER * DEPTH) {
@@ -951,7 +968,8 @@ OT_DEV void fuse_accum_body(const FuseOne& F, const FuseIndex& ix, const double*
 }
 // several detectors in one launch (blockIdx.z), their records in device memory
 __global__ __launch_bounds__(1024) void fuse_accum_multi_kernel(const FuseOne* __restrict__ dets, const FuseIndex* __restrict__ ixs, const double* __restrict__ table) {
-    fuse_accum_body(dets[blockIdx.z], ixs[blockIdx.z], table, blockIdx.x, gridDim.x);
+    const FuseOne& F = dets[blockIdx.z];
+    if (F.spread[0]) fuse_accum_body<TileRec>(F, ixs[blockIdx.z], table, blockIdx.x, gridDim.x);
 }
 
 // grid (16, K): thread = one pixel of tile blockIdx.y, all four planes
@@ -965,19 +983,12 @@ OT_DEV void fuse_reduce_body(const FuseOne& F, const FuseIndex& ix, const unsign
     const int px = (tl % F.tx) * OT_TILE_W + (local & (OT_TILE_W - 1));
     const int py = (tl / F.tx) * OT_TILE_W + (local >> 6);
     if (px >= F.a.Nx || py >= F.a.Ny) return;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (unsigned int s = s_first; s < s_end; s++) {
-        const double* sl = ix.slabs + (size_t)s * (OT_TILE_PX * 4) + local;  // plane-major slab
-        s0 += sl[0 * OT_TILE_PX];
-        s1 += sl[1 * OT_TILE_PX];
-        s2 += sl[2 * OT_TILE_PX];
-        s3 += sl[3 * OT_TILE_PX];
-    }
+    const Sum4 sum = slab_sum4(ix.slabs, s_first, s_end, local);
     double* hg = F.hist + ((int64_t)py * F.a.Nx + px) * 4;
-    hg[0] += s0;
-    hg[1] += s1;
-    hg[2] += s2;
-    hg[3] += s3;
+    hg[0] += sum.s0;
+    hg[1] += sum.s1;
+    hg[2] += sum.s2;
+    hg[3] += sum.s3;
 }
 // several detectors in one launch (blockIdx.z), their records in device memory
 __global__ __launch_bounds__(256) void fuse_reduce_multi_kernel(const FuseOne* __restrict__ dets, const FuseIndex* __restrict__ ixs) {
@@ -1004,13 +1015,6 @@ __global__ __launch_bounds__(256) void fuse_reduce_multi_kernel(const FuseOne* _
 //            the escape list are added straight to the image.                                      reads 24 B
 //
 // 104 B per ray instead of 136; same pixels and sums as the chain (the sums in another order).
-OT_DEV void spec_origin(const FuseOne& F, int t, int& ox, int& oy) {
-    const int tcx = t % F.g.tx, tcy = t / F.g.tx;
-    // one pixel of slack: membership in a tile was decided by floor((x - X0) / tw), its corner here is X0 + tcx * tw
-    ox = (int)floor(F.a.fx * (F.g.X0 + (double)tcx * F.g.tw - F.a.x0)) - 1;
-    oy = (int)floor(F.a.fy * (F.g.Y0 + (double)tcy * F.g.th - F.a.y0)) - 1;
-}
-
 // extent of the hits of a sample of the rays: wave k of the launch takes rays [64 k stride, 64 k stride + 64)
 __global__ __launch_bounds__(256) void spec_sample_kernel(ot_rays R, uint32_t count, const FuseOne* __restrict__ dets,
                                                           uint32_t stride) {
@@ -1053,91 +1057,7 @@ __global__ __launch_bounds__(64) void spec_result_kernel(const unsigned long lon
 
 // fuse_accum_body for SpecRec chunks: LDS window of tile t = final pixels [ox, ox + 64) x [oy, oy + 64)
 __global__ __launch_bounds__(1024) void spec_accum_kernel(FuseOne F, FuseIndex ix, const double* __restrict__ table) {
-    extern __shared__ double lds[];  // [TILE_PX * 4 window] [471 * 6 observer table: (value, difference) pairs]; the window part first holds wstart
-    double* tile = lds;
-    double* obs = lds + OT_TILE_PX * 4;
-    unsigned int* ws = (unsigned int*)lds;
-    const int K = F.K;
-    const unsigned int total = ix.wstart[K];  // (resident workgroups take the slabs in turn, see fuse_accum_body)
-    if (blockIdx.x >= total) return;
-    for (int i = threadIdx.x; i < OT_OBS_N * 6; i += blockDim.x) obs[i] = table[OT_OBS6_OFF + i];
-    for (unsigned int b = blockIdx.x; b < total; b += gridDim.x) {
-        for (int i = threadIdx.x; i <= K; i += blockDim.x) ws[i] = ix.wstart[i];
-        __syncthreads();
-        int lo = 0, hi = K;  // ws[lo] <= b < ws[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (ws[mid] <= b) lo = mid; else hi = mid;
-        }
-        const int t = lo;
-        const unsigned int part = b - ws[t];
-        __syncthreads();  // everyone has read ws: the window may be cleared
-        const unsigned int c0 = ix.tstart[t], n_t = ix.tstart[t + 1] - c0;
-        const unsigned int j_begin = part * OT_FUSE_CPW;
-        const unsigned int j_end = (j_begin + OT_FUSE_CPW < n_t) ? j_begin + OT_FUSE_CPW : n_t;
-        for (int i = threadIdx.x; i < OT_TILE_PX * 4; i += blockDim.x) tile[i] = 0.0;
-        __shared__ unsigned int s_chunk[OT_FUSE_CPW], s_fill[OT_FUSE_CPW];
-        for (unsigned int i = threadIdx.x; i < j_end - j_begin; i += blockDim.x) {
-            const unsigned int c = ix.list[c0 + j_begin + i];
-            s_chunk[i] = c;
-            s_fill[i] = F.chunk_fill[c];
-        }
-        __syncthreads();
-        int ox, oy;
-        spec_origin(F, t, ox, oy);
-        const SpecRec* __restrict__ recs = (const SpecRec*)F.rec;
-        constexpr int PER = 1024 / OT_FUSE_CH;
-        constexpr int DEPTH = 4;  // two stages of DEPTH records in flight per thread, see fuse_accum_body
-        const int g = threadIdx.x / OT_FUSE_CH, slot = threadIdx.x % OT_FUSE_CH;
-        const int n_c = (int)(j_end - j_begin);
-        auto load = [&](int first, SpecRec* rec, bool* ok) {
-    #pragma unroll
-            for (int k = 0; k < DEPTH; k++) {
-                const int i = first + k * PER, ic = i < n_c ? i : 0;
-                ok[k] = i < n_c && (unsigned int)slot < s_fill[ic];
-                if (ok[k]) rec[k] = recs[(size_t)s_chunk[ic] * OT_FUSE_CH + slot];
-            }
-        };
-        auto add = [&](const SpecRec* rec, const bool* ok) {
-    #pragma unroll
-            for (int k = 0; k < DEPTH; k++) {
-                if (!ok[k]) continue;
-                int32_t px, py;
-                const int pix = hit_pixel(F.a, rec[k].x, rec[k].y, px, py);
-                if (pix < 0) continue;
-                const double wm = (double)rec[k].w * F.a.ws;
-                double xo, yo, zo;
-                observer_xyz_at6(obs, (double)rec[k].wl, xo, yo, zo);
-                const int lx = px - ox, ly = py - oy;
-                if ((unsigned)lx < (unsigned)OT_TILE_W && (unsigned)ly < (unsigned)OT_TILE_W) {
-                    double* hv = tile + ((ly << 6) | lx);  // plane-major window, see fuse_accum_body
-                    unsafeAtomicAdd(hv + 0 * OT_TILE_PX, xo * wm);
-                    unsafeAtomicAdd(hv + 1 * OT_TILE_PX, yo * wm);
-                    unsafeAtomicAdd(hv + 2 * OT_TILE_PX, zo * wm);
-                    unsafeAtomicAdd(hv + 3 * OT_TILE_PX, 1.0 * wm);
-                } else {
-                    double* hg = F.hist + (int64_t)pix * 4;
-                    unsafeAtomicAdd(hg + 0, xo * wm);
-                    unsafeAtomicAdd(hg + 1, yo * wm);
-                    unsafeAtomicAdd(hg + 2, zo * wm);
-                    unsafeAtomicAdd(hg + 3, 1.0 * wm);
-                }
-            }
-        };
-        SpecRec ra[DEPTH], rb[DEPTH];
-        bool oa[DEPTH], ob[DEPTH];
-        load(g, ra, oa);
-        for (int i0 = g; i0 < n_c; i0 += 2 * PER * DEPTH) {
-            load(i0 + PER * DEPTH, rb, ob);
-            add(ra, oa);
-            load(i0 + 2 * PER * DEPTH, ra, oa);
-            add(rb, ob);
-        }
-        __syncthreads();
-        double* slab = ix.slabs + (size_t)b * (OT_TILE_PX * 4);
-        for (int i = threadIdx.x; i < OT_TILE_PX * 4; i += blockDim.x) slab[i] = tile[i];
-        __syncthreads();  // the slab is out: the window part holds wstart again in the next round
-    }
+    fuse_accum_body<SpecRec>(F, ix, table, blockIdx.x, gridDim.x);
 }
 
 // grid (16, K): thread = one pixel of the window of tile blockIdx.y, all four planes; windows overlap -> atomics
@@ -1150,20 +1070,9 @@ __global__ __launch_bounds__(256) void spec_reduce_kernel(FuseOne F, FuseIndex i
     spec_origin(F, tl, ox, oy);
     const int px = ox + (local & (OT_TILE_W - 1)), py = oy + (local >> 6);
     if (px < 0 || py < 0 || px >= F.a.Nx || py >= F.a.Ny) return;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (unsigned int s = s_first; s < s_end; s++) {
-        const double* sl = ix.slabs + (size_t)s * (OT_TILE_PX * 4) + local;
-        s0 += sl[0 * OT_TILE_PX];
-        s1 += sl[1 * OT_TILE_PX];
-        s2 += sl[2 * OT_TILE_PX];
-        s3 += sl[3 * OT_TILE_PX];
-    }
-    if (s3 == 0.0) return;  // (weights are positive: no hit in this pixel)
-    double* hg = F.hist + ((int64_t)py * F.a.Nx + px) * 4;
-    unsafeAtomicAdd(hg + 0, s0);
-    unsafeAtomicAdd(hg + 1, s1);
-    unsafeAtomicAdd(hg + 2, s2);
-    unsafeAtomicAdd(hg + 3, s3);
+    const Sum4 sum = slab_sum4(ix.slabs, s_first, s_end, local);
+    if (sum.s3 == 0.0) return;  // (weights are positive: no hit in this pixel)
+    add4(F.hist + ((int64_t)py * F.a.Nx + px) * 4, 1, sum.s0, sum.s1, sum.s2, sum.s3);
 }
 
 // the escape list: a few hits far outside the sample's extent, straight into the image
@@ -1177,10 +1086,6 @@ __global__ __launch_bounds__(256) void spec_escaped_kernel(FuseOne F, const doub
         double xo, yo, zo;
         observer_xyz_at(table, (double)r.wl, xo, yo, zo);
         const double wm = (double)r.w * F.a.ws;
-        double* hg = F.hist + (int64_t)pix * 4;
-        unsafeAtomicAdd(hg + 0, xo * wm);
-        unsafeAtomicAdd(hg + 1, yo * wm);
-        unsafeAtomicAdd(hg + 2, zo * wm);
-        unsafeAtomicAdd(hg + 3, 1.0 * wm);
+        add4_hit(F.hist + (int64_t)pix * 4, 1, xo, yo, zo, wm);
     }
 }

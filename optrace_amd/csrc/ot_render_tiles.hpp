@@ -64,6 +64,40 @@ OT_DEV int tile_of(const TileArgs& t, int32_t ix, int32_t iy, int& local) {
     return (iy >> 6) * t.tx + (ix >> 6);
 }
 
+// (a0, a1, a2, a3) added to the four planes of a pixel, `stride` doubles apart.  OT_TILE_PX: a plane-major LDS tile
+// [channel][pixel] -- the lanes of one add then spread over 16 bank pairs; pixel-major (4 doubles per pixel) would leave
+// them 4 and make every add a 16-way bank conflict.  1: the pixel-major image.
+OT_DEV void add4(double* p, int stride, double a0, double a1, double a2, double a3) {
+    unsafeAtomicAdd(p + 0 * stride, a0);
+    unsafeAtomicAdd(p + 1 * stride, a1);
+    unsafeAtomicAdd(p + 2 * stride, a2);
+    unsafeAtomicAdd(p + 3 * stride, a3);
+}
+// ... for a hit of weight wm with the observer's (xo, yo, zo) at its wavelength
+OT_DEV void add4_hit(double* p, int stride, double xo, double yo, double zo, double wm) {
+    unsafeAtomicAdd(p + 0 * stride, xo * wm);
+    unsafeAtomicAdd(p + 1 * stride, yo * wm);
+    unsafeAtomicAdd(p + 2 * stride, zo * wm);
+    unsafeAtomicAdd(p + 3 * stride, 1.0 * wm);
+}
+
+// the four planes of pixel `local` of a tile summed over the plane-major slabs [first, end)
+struct Sum4 {
+    double s0, s1, s2, s3;
+};
+template <class I>
+OT_DEV Sum4 slab_sum4(const double* slabs, I first, I end, int local) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (I s = first; s < end; s++) {
+        const double* sl = slabs + (size_t)s * (OT_TILE_PX * 4) + local;
+        s0 += sl[0 * OT_TILE_PX];
+        s1 += sl[1 * OT_TILE_PX];
+        s2 += sl[2 * OT_TILE_PX];
+        s3 += sl[3 * OT_TILE_PX];
+    }
+    return {s0, s1, s2, s3};
+}
+
 __global__ __launch_bounds__(1024) void tile_probe_kernel(TileArgs t, const double* __restrict__ px, const double* __restrict__ py,
                                                           const float* __restrict__ w, int* __restrict__ spread,
                                                           const unsigned int* __restrict__ fill) {
@@ -233,13 +267,7 @@ __global__ __launch_bounds__(1024) void tile_accum_kernel(TileArgs t, const doub
         const double wm = (double)rec.w * t.a.ws;
         double xo, yo, zo;
         observer_xyz_at6(obs, (double)rec.wl, xo, yo, zo);
-        // plane-major tile [channel][pixel]: the lanes of one add spread over 16 bank pairs (with 4 doubles per pixel
-        // they share 4, a 16-way bank conflict on every add)
-        double* hv = tile + (int)rec.px;
-        unsafeAtomicAdd(hv + 0 * OT_TILE_PX, xo * wm);
-        unsafeAtomicAdd(hv + 1 * OT_TILE_PX, yo * wm);
-        unsafeAtomicAdd(hv + 2 * OT_TILE_PX, zo * wm);
-        unsafeAtomicAdd(hv + 3 * OT_TILE_PX, 1.0 * wm);
+        add4_hit(tile + (int)rec.px, OT_TILE_PX, xo, yo, zo, wm);
     }
     __syncthreads();
     double* slab = wk.slabs + (size_t)c * (OT_TILE_PX * 4);
@@ -256,17 +284,10 @@ __global__ __launch_bounds__(256) void tile_reduce_kernel(TileArgs t, TileWork w
     const int ix = (tl % t.tx) * OT_TILE_W + (local & (OT_TILE_W - 1));
     const int iy = (tl / t.tx) * OT_TILE_W + (local >> 6);
     if (ix >= t.a.Nx || iy >= t.a.Ny) return;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (int c = c0; c < c1; c++) {
-        const double* sl = wk.slabs + (size_t)c * (OT_TILE_PX * 4) + local;  // plane-major slab
-        s0 += sl[0 * OT_TILE_PX];
-        s1 += sl[1 * OT_TILE_PX];
-        s2 += sl[2 * OT_TILE_PX];
-        s3 += sl[3 * OT_TILE_PX];
-    }
+    const Sum4 sum = slab_sum4(wk.slabs, c0, c1, local);
     double* hg = hist + ((int64_t)iy * t.a.Nx + ix) * 4;
-    hg[0] += s0;
-    hg[1] += s1;
-    hg[2] += s2;
-    hg[3] += s3;
+    hg[0] += sum.s0;
+    hg[1] += sum.s1;
+    hg[2] += sum.s2;
+    hg[3] += sum.s3;
 }
