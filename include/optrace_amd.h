@@ -412,6 +412,24 @@ int ot_scene_last_trace_ms(const ot_scene* scene, double* ms);
 int ot_scene_set_index_store(ot_scene* scene, int32_t on);
 int ot_rays_fill_index(const ot_scene* scene, const ot_rays* rays, int64_t first, int64_t count, void* stream);
 
+/* The planes a trace may leave unwritten, as one mask per scene (default 0: complete storage).  OT_DEFER_INDEX is the
+ * switch above.  OT_DEFER_POL: ot_generate_and_trace and ot_generate_and_trace_host leave rays->pol untouched (it must
+ * still be a valid buffer when polarisation is on); the polarisation is computed as before -- the weights depend on it --
+ * and nothing in this library reads the planes after the trace.  ot_trace stores them whatever the mask: its input
+ * polarisation lives in section 0 of the plane and its rays cannot be repeated.
+ * ot_scene_set_index_store is defined through the mask: on = 1 clears the WHOLE mask (every plane is stored), on = 0 sets
+ * OT_DEFER_INDEX and leaves the other bits.
+ * ot_rays_fill_pol writes pol[:, :, ray] of the rays [first, first + count) by repeating the trace: a trace that generates
+ * its rays on the device is a function of (scene, sources, ranges, seed) alone, so with the arguments of that trace the
+ * planes are bit for bit what it stores without OT_DEFER_POL.  `ranges` must cover the storage as they did for the trace,
+ * rays->nt must be the scene's section count and the scene must track polarisation; only rays->N, nt and pol are used.
+ * Counters are not touched and a hit-search timeout is not reported.  Asynchronous on `stream`. */
+#define OT_DEFER_INDEX 1u
+#define OT_DEFER_POL 2u
+int ot_scene_set_deferred_planes(ot_scene* scene, uint32_t mask);
+int ot_rays_fill_pol(const ot_scene* scene, const ot_sources* sources, const ot_source_range* ranges, int32_t n_ranges,
+                     uint64_t seed, const ot_rays* rays, int64_t first, int64_t count, void* stream);
+
 /* ---- leaf operators (public Surface / RefractionIndex methods) ---------------------------------- */
 /* Surface.find_hit (surface.py:307, conic_surface.py:126): p, s are (n,3) F-order device arrays;
  * outputs p_hit (n,3) F-order, is_hit (n) uint8, ill (n) uint8: bit 0 = ill-conditioned bracket

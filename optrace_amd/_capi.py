@@ -155,6 +155,8 @@ SIGNATURES = {
     "ot_scene_last_trace_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "ot_scene_set_index_store": (C.c_int, [vp, i32]),
     "ot_rays_fill_index": (C.c_int, [vp, C.POINTER(Rays), i64, i64, vp]),
+    "ot_scene_set_deferred_planes": (C.c_int, [vp, C.c_uint32]),
+    "ot_rays_fill_pol": (C.c_int, [vp, vp, C.POINTER(SourceRange), i32, u64, C.POINTER(Rays), i64, i64, vp]),
     "ot_surface_find_hit": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp, vp, vp]),
     "ot_surface_normals": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp]),
     "ot_surface_mask": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp]),
@@ -193,6 +195,7 @@ FOCUS_WS = 16  # OT_FOCUS_WS
 HIT_PIECES = 1024  # OT_HIT_PIECES
 ABI_VERSION = 9  # OT_ABI_VERSION
 ERR_UNSUPPORTED = -3  # OT_ERR_UNSUPPORTED
+OT_DEFER_INDEX, OT_DEFER_POL = 1, 2  # ot_scene_set_deferred_planes
 
 _lib = None
 

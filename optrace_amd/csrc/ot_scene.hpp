@@ -110,8 +110,9 @@ struct ot_scene {
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
-    // ot_scene_set_index_store: off = the trace kernels leave the plane ot_rays.n unwritten (ot_rays_fill_index writes it)
-    bool index_store = true;
+    // ot_scene_set_deferred_planes: OT_DEFER_* bits of the planes the generating trace kernels leave unwritten (ot_rays.n:
+    // ot_rays_fill_index writes it; ot_rays.pol: ot_rays_fill_pol)
+    uint32_t deferred = 0;
     // SPEC of the last stored trace (0 formulas, 1 + tables, 2 per-line tables; -1: none yet): ot_rays_fill_index evaluates
     // the indices the way that launch did
     int index_spec = -1;

@@ -490,10 +490,18 @@ extern "C" int ot_scene_set_timing(ot_scene* sc, int32_t on) {
 
 // The index plane ot_rays.n is a function of (scene, section, wavelength) alone and nothing in the library reads it: a caller
 // who does not need it after every trace switches its stores off and writes it with ot_rays_fill_index when it is asked for.
+// The polarisation planes can be repeated from (scene, sources, ranges, seed) by ot_rays_fill_pol.  One mask holds both.
+extern "C" int ot_scene_set_deferred_planes(ot_scene* sc, uint32_t mask) {
+    if (!sc) return fail(OT_ERR_INVALID, "ot_scene_set_deferred_planes: null scene");
+    if (mask & ~(uint32_t)(OT_DEFER_INDEX | OT_DEFER_POL)) return fail(OT_ERR_INVALID, "ot_scene_set_deferred_planes: unknown bit in the mask");
+    sc->deferred = mask;
+    return OT_OK;
+}
+
+// on: complete storage, every plane (the whole mask is cleared); off: OT_DEFER_INDEX joins the mask
 extern "C" int ot_scene_set_index_store(ot_scene* sc, int32_t on) {
     if (!sc) return fail(OT_ERR_INVALID, "ot_scene_set_index_store: null scene");
-    sc->index_store = on != 0;
-    return OT_OK;
+    return ot_scene_set_deferred_planes(sc, on ? 0u : (sc->deferred | OT_DEFER_INDEX));
 }
 
 extern "C" int ot_scene_last_trace_ms(const ot_scene* sc, double* ms) {

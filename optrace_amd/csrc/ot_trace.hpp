@@ -323,7 +323,7 @@ OT_DEV void store_section(const ot_rays& R, uint32_t o8, uint32_t o4, int sec, c
     store_f64(R.p + N * (sec + 2 * nt), o8, p.z);
     store_f32(R.w + N * sec, o4, w);
     if (R.n) store_f64(R.n + N * sec, o8, n);  // (null: see store_section_next)
-    if (POL) {
+    if (POL && R.pol) {
         store_f32(R.pol + N * sec, o4, px);
         store_f32(R.pol + N * (sec + nt), o4, py);
         store_f32(R.pol + N * (sec + 2 * nt), o4, pz);
@@ -341,12 +341,19 @@ template <bool POL>
 OT_DEV PlaneBases plane_bases(const ot_rays& R) {
     const int64_t N = R.N, nt = R.nt;
     PlaneBases b = {R.p, R.p + N * nt, R.p + N * 2 * nt, R.n, R.w, nullptr, nullptr, nullptr, N};
-    if (POL) {
+    if (POL && R.pol) {  // (null: the polarisation planes are deferred, see store_section_next)
         b.qx = R.pol;
         b.qy = R.pol + N * nt;
         b.qz = R.pol + N * 2 * nt;
     }
     return b;
+}
+// the polarisation planes of one section alone (ot_rays_fill_pol's kernel stores nothing else)
+OT_DEV void store_pol_next(PlaneBases& b, uint32_t o4, float px, float py, float pz) {
+    store_f32(b.qx, o4, px);
+    store_f32(b.qy, o4, py);
+    store_f32(b.qz, o4, pz);
+    b.qx += b.N, b.qy += b.N, b.qz += b.N;
 }
 template <bool POL>
 OT_DEV void store_section_next(PlaneBases& b, uint32_t o8, uint32_t o4, const V3& p, float w, double n, float px, float py,
@@ -364,12 +371,11 @@ OT_DEV void store_section_next(PlaneBases& b, uint32_t o8, uint32_t o4, const V3
         b.n += b.N;
     }
     b.px += b.N, b.py += b.N, b.pz += b.N, b.w += b.N;
-    if (POL) {
-        store_f32(b.qx, o4, px);
-        store_f32(b.qy, o4, py);
-        store_f32(b.qz, o4, pz);
-        b.qx += b.N, b.qy += b.N, b.qz += b.N;
-    }
+    // The polarisation planes (12 of 40 B per section) are read when somebody inspects single rays, and a trace that
+    // generates its rays on the device can be repeated: with OT_DEFER_POL (ot_scene_set_deferred_planes) the launcher hands
+    // in a null base as well and ot_rays_fill_pol writes the planes later.  The polarisation itself is still computed: the
+    // weights depend on it.
+    if (POL && b.qx) store_pol_next(b, o4, px, py, pz);
 }
 #ifndef OT_RUNNING_BASES
 #define OT_RUNNING_BASES 1
@@ -393,11 +399,19 @@ struct TailState {
     V3 p;
     float w;
 };
-template <bool POL, int SPEC, int FEAT, bool TAIL = false, class SC>
+// What trace_ray stores: every plane (trace_kernel) / nothing, the TAIL form above / the polarisation planes alone
+// (trace_pol_kernel: the replay behind ot_rays_fill_pol -- the same arithmetic, `R` needs pol, N and nt only).
+#define OT_STORE_ALL 0
+#define OT_STORE_NONE 1
+#define OT_STORE_POL 2
+template <bool POL, int SPEC, int FEAT, int STORE = OT_STORE_ALL, class SC>
 OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, RayState& r,
                       const double* __restrict__ hurb_normals, uint64_t seed, unsigned int* msgs, const double* ltab,
                       int lj, double* patch_lds, TailState* tail = nullptr) {
     constexpr bool TAB = (SPEC == 1);
+    constexpr bool TAIL = (STORE == OT_STORE_NONE);
+    constexpr bool ALL = (STORE == OT_STORE_ALL);
+    constexpr bool POL_ONLY = (STORE == OT_STORE_POL);
     constexpr bool FULL = (FEAT & 1) != 0;  // HURB -- and, at hit level 0, ideal lenses and filters
     constexpr int LEVEL = FEAT / 2;         // hit level (ot_device.hpp): closed form / + Illinois search / + spline surfaces
     // Ideal lenses and filters cost 2-4 registers: the levels with a numeric hit search carry them always (their scenes
@@ -425,12 +439,11 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
     r.n_cur = (SPEC == 2) ? lrow[(3 * sc.n_steps) * OT_MAX_LINES] : medium_n<TAB>(media[sc.n0], pool, r.wl);
 #if OT_RUNNING_BASES
     PlaneBases planes = {};
-    if (!TAIL) {
-        planes = plane_bases<POL>(R);
-        store_section_next<POL>(planes, o8, o4, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
-    }
+    if (!TAIL) planes = plane_bases<POL>(R);
+    if (ALL) store_section_next<POL>(planes, o8, o4, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+    if (POL_ONLY) store_pol_next(planes, o4, r.polx, r.poly, r.polz);
 #else
-    if (!TAIL) store_section<POL>(R, o8, o4, 0, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+    if (ALL) store_section<POL>(R, o8, o4, 0, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
 #endif
 
     for (int i = 0; i < sc.n_steps; i++) {  // i = index of the section the ray starts this step in
@@ -518,13 +531,16 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
 #ifdef OT_NO_SECTION_STORES  // experiment (tools/power_clock.py): the same arithmetic, only the last section is stored
         if (i + 1 == sc.n_steps)
 #endif
+        {
 #if OT_RUNNING_BASES
-        if (!TAIL) store_section_next<POL>(planes, o8, o4, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+            if (ALL) store_section_next<POL>(planes, o8, o4, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+            if (POL_ONLY) store_pol_next(planes, o4, r.polx, r.poly, r.polz);
 #else
-        if (!TAIL) store_section<POL>(R, o8, o4, i + 1, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+            if (ALL) store_section<POL>(R, o8, o4, i + 1, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
 #endif
+        }
     }
-    if (!TAIL) {
+    if (ALL) {
         const int64_t N = R.N;
         store_f64(R.s, o8, r.s.x);
         store_f64(R.s + N, o8, r.s.y);

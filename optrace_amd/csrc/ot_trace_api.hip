@@ -86,6 +86,36 @@ extern "C" int ot_rays_generate(const ot_sources* src, const ot_source_range* ra
     return OT_OK;
 }
 
+// Which kernel variant traces a scene, and its dynamic LDS: spectrum handling x feature set (polarisation and on-device
+// generation follow from the scene and the entry point).  ot_rays_fill_pol repeats a trace with the variant chosen here.
+struct TraceVariant {
+    int feat, spec;
+    size_t lds;
+    const char* error;
+};
+static TraceVariant trace_variant(const ot_scene* sc, const ot_sources* src, const double* hurb_normals) {
+    const int n_cnt = OT_N_INFOS * sc->h.nt + 1;
+    const bool tab = sc->needs_tables || hurb_normals != nullptr;
+    TraceVariant v = {OT_FEAT(sc->hit_level, sc->needs_full), 0, 0, nullptr};
+    // discrete-spectrum kernels: generated rays only, and no image source (their variant of the generator has none)
+    bool lines = src != nullptr && sc->h.n_lines > 0 && hurb_normals == nullptr && !src->has_image;
+    // dynamic LDS: the counter table, and with discrete spectra the per-line tables (3 rows per step).  Very long
+    // stacks do not fit the 64 KB a kernel gets without asking: the formula kernels (SPEC 0 / 1) trace those.
+    const size_t lds_cnt = sizeof(unsigned int) * (size_t)n_cnt + 8;
+    const size_t lds_lines = sizeof(double) * (size_t)(3 * sc->h.n_steps + 2) * OT_MAX_LINES;
+    // spline surfaces: a 5 x 5 coefficient patch per lane (ot_spline.hpp::PatchCache)
+    const size_t lds_patch = (sc->hit_level == OT_HIT_SPLINE) ? 256 * 25 * sizeof(double) + 16 : 0;
+    if (lds_cnt + lds_patch > 65000) {
+        v.error = lds_patch ? "ot_trace: more than ~650 tracing surfaces in a scene with spline surfaces"
+                            : "ot_trace: more than ~3000 tracing surfaces in one scene";
+        return v;
+    }
+    if (lines && lds_cnt + lds_lines + lds_patch > 65000) lines = false;
+    v.lds = ((lds_cnt + (lines ? lds_lines : 0) + 7) / 8) * 8 + lds_patch;
+    v.spec = lines ? 2 : (tab ? 1 : 0);
+    return v;
+}
+
 // msgs: device counters the launch ADDS to, or nullptr: the counters of this launch alone go to the scene's pinned
 // host buffer (created on first use)
 // tail: render-only launch (trace_tail_kernel) of n_tail rays -- `rays` is not used then
@@ -122,24 +152,11 @@ static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const Range
     const SourceDev* sd = src ? src->d : nullptr;
     unsigned long long* m = (unsigned long long*)msgs;
     if (!msgs) HIP_TRY(hipHostGetDevicePointer((void**)&m, sc->pin_msgs, 0));
-    // kernel variant: polarisation x on-device generation x spectrum handling x feature set
-    const bool tab = sc->needs_tables || hurb_normals != nullptr;
-    const int feat = OT_FEAT(sc->hit_level, sc->needs_full);
-    // discrete-spectrum kernels: generated rays only, and no image source (their variant of the generator has none)
-    bool lines = src != nullptr && sc->h.n_lines > 0 && hurb_normals == nullptr && !src->has_image;
-    // dynamic LDS: the counter table, and with discrete spectra the per-line tables (3 rows per step).  Very long
-    // stacks do not fit the 64 KB a kernel gets without asking: the formula kernels (SPEC 0 / 1) trace those.
-    const size_t lds_cnt = sizeof(unsigned int) * (size_t)n_cnt + 8;
-    const size_t lds_lines = sizeof(double) * (size_t)(3 * sc->h.n_steps + 2) * OT_MAX_LINES;
-    // spline surfaces: a 5 x 5 coefficient patch per lane (ot_spline.hpp::PatchCache)
-    const size_t lds_patch = (sc->hit_level == OT_HIT_SPLINE) ? 256 * 25 * sizeof(double) + 16 : 0;
-    if (lds_cnt + lds_patch > 65000)
-        return fail(OT_ERR_UNSUPPORTED, lds_patch ? "ot_trace: more than ~650 tracing surfaces in a scene with spline surfaces"
-                                                  : "ot_trace: more than ~3000 tracing surfaces in one scene");
-    if (lines && lds_cnt + lds_lines + lds_patch > 65000) lines = false;
-    const size_t lds = ((lds_cnt + (lines ? lds_lines : 0) + 7) / 8) * 8 + lds_patch;
+    const TraceVariant v = trace_variant(sc, src, hurb_normals);
+    if (v.error) return fail(OT_ERR_UNSUPPORTED, v.error);
+    const int feat = v.feat, spec = v.spec;
+    const size_t lds = v.lds;
     unsigned int* slots = sc->cnt_slots;
-    const int spec = lines ? 2 : (tab ? 1 : 0);
     if (!tail) sc->index_spec = spec;  // what ot_rays_fill_index has to repeat
     if (sc->timing) HIP_TRY(hipEventRecord(sc->ev0, st));
     // lanes address their ray with 32-bit byte offsets: launches of at most 2^28 rays, base pointers advanced
@@ -155,7 +172,10 @@ static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const Range
         if (!tail) {
             L.part.p += base; L.part.s += base; L.part.w += base; L.part.n += base; L.part.wl += base;
             if (L.part.pol) L.part.pol += base;
-            if (!sc->index_store) L.part.n = nullptr;  // the kernel skips the plane (ot_trace.hpp::store_section_next)
+            // deferred planes: a null base, the kernel skips the plane (ot_trace.hpp::store_section_next).  Rays handed in
+            // cannot be repeated and carry their polarisation in section 0 of the plane: ot_trace always stores it.
+            if (sc->deferred & OT_DEFER_INDEX) L.part.n = nullptr;
+            if ((sc->deferred & OT_DEFER_POL) && src) L.part.pol = nullptr;
         }
         L.sd = sd;
         L.rg = &r;
@@ -287,6 +307,55 @@ extern "C" int ot_rays_fill_index(const ot_scene* sc, const ot_rays* rays, int64
             hipLaunchKernelGGL(fill_index_kernel<1>, grid_for(n), dim3(256), 0, st, sc->d, wl, plane, rays->N, n);
         else
             hipLaunchKernelGGL(fill_index_kernel<0>, grid_for(n), dim3(256), 0, st, sc->d, wl, plane, rays->N, n);
+    }
+    HIP_TRY(hipGetLastError());
+    return OT_OK;
+}
+
+// The polarisation planes of a storage whose trace left them unwritten (OT_DEFER_POL): the trace once more, storing only them
+// (ot_trace_kernel.hpp::trace_pol_kernel).  Chunks and base advances as in launch_trace.
+extern "C" int ot_rays_fill_pol(const ot_scene* sc, const ot_sources* src, const ot_source_range* ranges, int32_t n_ranges,
+                                uint64_t seed, const ot_rays* rays, int64_t first, int64_t count, void* stream) {
+    if (!sc || !src || !ranges || !rays) return fail(OT_ERR_INVALID, "ot_rays_fill_pol: null argument");
+    if (sc->h.no_pol) return fail(OT_ERR_INVALID, "ot_rays_fill_pol: the scene does not track polarisation");
+    if (rays->N < 0 || !rays->pol) return fail(OT_ERR_INVALID, "ot_rays_fill_pol: the ray storage needs pol");
+    if (rays->nt != sc->h.nt || rays->nt != sc->h.n_steps + 1)
+        return fail(OT_ERR_INVALID, "ot_rays_fill_pol: ray storage has " + std::to_string(rays->nt) + " sections, the scene needs " +
+                                        std::to_string(sc->h.nt));
+    if (first < 0 || count < 0 || first > rays->N || count > rays->N - first)
+        return fail(OT_ERR_INVALID, "ot_rays_fill_pol: range outside the storage");
+    if (int rc = require_device()) return rc;
+    const RangeArgs* rg = nullptr;
+    if (int rc = make_ranges(ranges, n_ranges, src, rays->N, &rg)) return rc;
+    const TraceVariant v = trace_variant(sc, src, nullptr);
+    if (v.error) return fail(OT_ERR_UNSUPPORTED, v.error);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t chunk = 1ll << 28;
+    for (int64_t base = first; base < first + count; base += chunk) {
+        TraceLaunch L = {};
+        L.count = (uint32_t)std::min<int64_t>(chunk, first + count - base);
+        L.grid = grid_for(L.count);
+        L.lds = v.lds;
+        L.st = st;
+        L.sc = sc->d;
+        L.part = {};  // the kernel reads N, nt and pol
+        L.part.N = rays->N;
+        L.part.nt = rays->nt;
+        L.part.pol = rays->pol + base;
+        L.sd = src->d;
+        L.rg = rg;
+        L.seed = seed;
+        L.base = base;
+        L.pol = L.gen = true;
+        L.spec = v.spec;
+        switch (v.feat) {
+            case OT_FEAT(OT_HIT_CLOSED, 0): launch_trace_pol_feat<OT_FEAT(OT_HIT_CLOSED, 0)>(L); break;
+            case OT_FEAT(OT_HIT_CLOSED, 1): launch_trace_pol_feat<OT_FEAT(OT_HIT_CLOSED, 1)>(L); break;
+            case OT_FEAT(OT_HIT_ILLINOIS, 0): launch_trace_pol_feat<OT_FEAT(OT_HIT_ILLINOIS, 0)>(L); break;
+            case OT_FEAT(OT_HIT_ILLINOIS, 1): launch_trace_pol_feat<OT_FEAT(OT_HIT_ILLINOIS, 1)>(L); break;
+            case OT_FEAT(OT_HIT_SPLINE, 0): launch_trace_pol_feat<OT_FEAT(OT_HIT_SPLINE, 0)>(L); break;
+            default: launch_trace_pol_feat<OT_FEAT(OT_HIT_SPLINE, 1)>(L); break;
+        }
     }
     HIP_TRY(hipGetLastError());
     return OT_OK;

@@ -1,7 +1,8 @@
 // The tracing kernel and its launch plumbing, shared by the translation units that instantiate its variants.
 //
 // One translation unit per feature level (ot_trace_f<level>.hip) instantiates the 10 variants of that level
-// (polarisation x generation x spectrum handling); ot_trace_api.hip only calls launch_trace_feat<level>().  The split is a
+// (polarisation x generation x spectrum handling); ot_trace_api.hip only calls launch_trace_feat<level>().  The render-only
+// form and the polarisation replay have units of their own (ot_trace_t<level>.hip, ot_trace_p<level>.hip).  The split is a
 // build-time matter (the variants compile in parallel, one level rebuilds alone) and changes nothing in the kernels.
 #pragma once
 #include "ot_trace.hpp"
@@ -314,7 +315,7 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ta
         const ot_rays none = {};
         // spline level: 25 doubles per lane behind the counters for the spline patch cache (as in trace_kernel)
         double* patch = (FEAT / 2 >= OT_HIT_SPLINE) ? lds + n_tab + (n_cnt + 2) / 2 : nullptr;
-        bool ok = trace_ray<POL, SPEC, FEAT, true>(sc, none, local, (uint64_t)ray, r, (const double*)nullptr, seed, cnt, ltab, lj,
+        bool ok = trace_ray<POL, SPEC, FEAT, OT_STORE_NONE>(sc, none, local, (uint64_t)ray, r, (const double*)nullptr, seed, cnt, ltab, lj,
                                                    patch, &tail);
         if (!ok) cnt[n_cnt - 1] = 1u;
     }
@@ -351,6 +352,50 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ta
         if (cnt[k]) atomicAdd(&slot_tab[k], cnt[k]);
 }
 
+// ---- the polarisation planes, replayed (ot_rays_fill_pol) -------------------------------------------------------------------
+// A trace that generates its rays on the device is a pure function of (scene, source table, source ranges, seed): generation
+// and the HURB deviates are Philox streams keyed by (seed, ray).  With OT_DEFER_POL the storing kernel leaves pol[3, nt, N]
+// unwritten; this kernel is trace_kernel<true, true, SPEC, FEAT> once more -- the same generate_lane, the same trace_ray -- with
+// the polarisation stores as its only stores (OT_STORE_POL), so the planes come out bit for bit as the storing kernel writes
+// them.  The event counters stay in LDS (count_event needs the table) and are not flushed, and a hit-search timeout is not
+// reported: the trace that is being repeated has done both.
+template <int SPEC, int FEAT>
+__global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, true)) void trace_pol_kernel(
+    const SceneDev* __restrict__ scp, ot_rays R, const SourceDev* __restrict__ sources, RangeArgs rg, uint64_t seed,
+    int64_t ray_base, uint32_t count) {
+    extern __shared__ double lds[];  // as in trace_kernel
+    auto& sc = *as_const(scp);
+    const int n_tab = (SPEC == 2) ? (3 * sc.n_steps + 2) * OT_MAX_LINES : 0;
+    double* ltab = lds;
+    unsigned int* cnt = (unsigned int*)(lds + n_tab);
+    const int n_cnt = OT_N_INFOS * sc.nt + 1;
+    for (int k = threadIdx.x; k < n_cnt; k += blockDim.x) cnt[k] = 0u;
+    if (SPEC == 2)
+        for (int k = threadIdx.x; k < n_tab; k += blockDim.x) ltab[k] = sc.line_tab[k];
+    __syncthreads();
+
+    const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t ray = ray_base + (int64_t)local;
+    if (local >= count) return;
+    NewRay nr;
+    if (!generate_lane<(SPEC != 2)>(rg, sources, ray, seed, false, nr)) return;
+    RayState r;
+    r.p = nr.p;
+    r.s = nr.s;
+    r.w = nr.w;
+    r.wl = nr.wl;
+    r.polx = (float)nr.polx;
+    r.poly = (float)nr.poly;
+    r.polz = (float)nr.polz;
+    int lj = 0;
+    if (SPEC == 2) {
+        for (int j = 1; j < sc.n_lines; j++)
+            if ((float)ltab[j] == r.wl) lj = j;
+    }
+    double* patch = (FEAT / 2 >= OT_HIT_SPLINE) ? lds + n_tab + (n_cnt + 2) / 2 : nullptr;
+    trace_ray<true, SPEC, FEAT, OT_STORE_POL>(sc, R, local, (uint64_t)ray, r, (const double*)nullptr, seed, cnt, ltab, lj, patch);
+}
+
 // Feature levels of the kernel variants.  Bit 0 ("full"): HURB, and at hit level 0 ideal lenses and filters as well (the
 // higher hit levels always carry those two, see trace_ray).  Upper part = hit level:
 //   OT_HIT_CLOSED   flat and conic surfaces (closed-form hit)
@@ -384,6 +429,22 @@ void launch_trace_feat(const TraceLaunch& L);
 // render-only variants (generation on the device, no injected HURB normals): defined in ot_trace_t<FEAT>.hip
 template <int FEAT>
 void launch_trace_tail_feat(const TraceLaunch& L, const TailOut& T);
+
+// polarisation replay (generation on the device, polarisation on): defined in ot_trace_p<FEAT>.hip
+template <int FEAT>
+void launch_trace_pol_feat(const TraceLaunch& L);
+
+#define OT_DEFINE_TRACE_POL_LAUNCHER(FEAT)                                                                              \
+    template <>                                                                                                         \
+    void launch_trace_pol_feat<FEAT>(const TraceLaunch& L) {                                                            \
+        const dim3 block(256);                                                                                          \
+        auto go = [&](auto kern) {                                                                                      \
+            hipLaunchKernelGGL(kern, L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg, L.seed, L.base, L.count);   \
+        };                                                                                                              \
+        if (L.spec == 2) go(trace_pol_kernel<2, FEAT>);                                                                 \
+        else if (L.spec == 1) go(trace_pol_kernel<1, FEAT>);                                                            \
+        else go(trace_pol_kernel<0, FEAT>);                                                                             \
+    }
 
 #define OT_DEFINE_TRACE_TAIL_LAUNCHER(FEAT)                                                                             \
     template <>                                                                                                         \

@@ -128,8 +128,9 @@ class SceneRef:
 
 
 class _DeviceBuffers(dict):
-    """name -> flat device tensor of a `RayStorage`.  A plain dict but for the key "n": the tracer's scenes leave the index
-    plane unwritten (`ot_scene_set_index_store`), so reading that entry first lets the storage fill it (`_ensure_index`)."""
+    """name -> flat device tensor of a `RayStorage`.  A plain dict but for the keys "n" and "pol": the tracer's scenes leave
+    the index plane and the polarisation planes unwritten (`ot_scene_set_deferred_planes`), so reading one of these entries
+    first lets the storage fill it (`_ensure_index`, `_ensure_pol`)."""
 
     __slots__ = ("_owner",)
 
@@ -142,6 +143,10 @@ class _DeviceBuffers(dict):
             owner = self._owner()
             if owner is not None:
                 owner._ensure_index()
+        elif key == "pol":
+            owner = self._owner()
+            if owner is not None:
+                owner._ensure_pol()
 
     def __getitem__(self, key):
         self._touch(key)
@@ -181,6 +186,11 @@ class RayStorage(BaseClass):
         self._n_stale = False
         self._n_scene = None
         self._n_count = 0
+        # The polarisation planes `_dev["pol"]` likewise: a trace that generates its rays on the device leaves them alone
+        # and can be repeated, so the mark holds what that takes -- (scene, source table, ranges, seed, ray count) -- and
+        # keeps scene, table and ranges alive until the planes are filled or another trace overwrites the mark
+        # (`_pol_pending`, `_ensure_pol`).
+        self._pol_stale = None
         self._powers = []
         self._ranges = None   # ot_source_range array of the current split (`_source_ranges`)
         self._rays_c = None   # ot_rays of the current buffers
@@ -225,18 +235,20 @@ class RayStorage(BaseClass):
         if not _alloc:
             d["_dev"], d["_rays_c"], d["_host"] = _DeviceBuffers(self), None, {}
             d["_N"], d["_Np"], d["_nt"] = N, N, nt
-            d["_n_stale"], d["_n_scene"] = False, None
+            d["_n_stale"], d["_n_scene"], d["_pol_stale"] = False, None, None
             return
         Np = -(-N // self.PAD_TO) * self.PAD_TO if N >= self.PAD_FROM else N
         old = self._dev
-        reuse = bool(old and self._N == N and self._Np == Np and self._nt == nt and (old["pol"] is None) == bool(no_pol)
-                     and old["p"].device == dev)
+        # (whether there are polarisation planes, not what they hold: read past the hook of `_dev`, no fill)
+        reuse = bool(old and self._N == N and self._Np == Np and self._nt == nt
+                     and (dict.get(old, "pol") is None) == bool(no_pol) and old["p"].device == dev)
         del old
         if not reuse:
             # (a trace with the shape of the previous one writes into the same buffers: host views already handed
             # out are copies, and nothing on the device outlives the trace that produced it)
             d["_dev"] = _DeviceBuffers(self)  # the previous storage goes back to the allocator before the new one is requested
             d["_n_stale"], d["_n_scene"] = True, None  # a fresh plane: nothing to fill it from until a trace says so
+            d["_pol_stale"] = None
 
             def alloc() -> dict:
                 return {
@@ -290,10 +302,12 @@ class RayStorage(BaseClass):
         d = self._dev
         r = _capi.Rays()
         r.N, r.nt = self._Np, self._nt  # the plane stride; how many rays there are, the ranges / counts of each call say
-        # (the address of the index plane, not its contents: read past the hook of `_dev`, no fill)
+        # (the addresses of the index plane and the polarisation planes, not their contents: read past the hook of `_dev`,
+        # no fill)
         r.p, r.s, r.w, r.n, r.wl = (d["p"].data_ptr(), d["s"].data_ptr(), d["w"].data_ptr(),
                                     dict.__getitem__(d, "n").data_ptr(), d["wl"].data_ptr())
-        r.pol = d["pol"].data_ptr() if d["pol"] is not None else None
+        pol = dict.__getitem__(d, "pol")
+        r.pol = pol.data_ptr() if pol is not None else None
         self.__dict__["_rays_c"] = r
         return r
 
@@ -313,6 +327,25 @@ class RayStorage(BaseClass):
                                                             stream_ptr()))
         d = self.__dict__  # (after the launch: a call that fails leaves the plane marked and its scene held)
         d["_n_stale"], d["_n_scene"] = False, None
+
+    def _pol_pending(self, scene: SceneRef, table: "SourceTable", ranges, seed: int, count: int) -> None:
+        """A trace of `scene` that generates its rays from (`table`, `ranges`, `seed`) is about to write this storage and
+        leaves the polarisation planes alone: rays [0, count) of them are to be written by repeating that trace when the
+        planes are read.  `scene=None` clears the mark (rays handed in: `ot_trace` stores the planes itself).  The storage
+        holds scene, table and ranges until then (a source table with function orientations exists for one trace only)."""
+        keep = scene is not None and dict.get(self._dev, "pol") is not None
+        self.__dict__["_pol_stale"] = (scene, table, ranges, int(seed), int(count)) if keep else None
+
+    def _ensure_pol(self) -> None:
+        """Write the polarisation planes if they are stale (`ot_rays_fill_pol`: the trace once more on the current stream,
+        storing only them; no synchronisation, no host copy).  Called by `_dev` whenever its entry "pol" is read."""
+        mark = self._pol_stale
+        if mark is None:
+            return
+        scene, table, ranges, seed, count = mark
+        _capi.check(_capi.load_library().ot_rays_fill_pol(scene.handle, table.handle, ranges, len(ranges), seed,
+                                                          C.byref(self._rays_struct()), 0, count, stream_ptr()))
+        self.__dict__["_pol_stale"] = None  # (after the launch: a call that fails leaves the planes marked)
 
     # blocks below this size are not cut further (their share of the rays, and of the time, is negligible)
     _MIN_BLOCK = 1 << 16
@@ -396,6 +429,7 @@ class RayStorage(BaseClass):
     def set_initial_rays(self, p, s, pols, w, wl) -> None:
         """Inject section 0 from host arrays (used for parity runs against recorded reference rays)."""
         N, Np, nt, dev = self._N, self._Np, self._nt, require_device()
+        self.__dict__["_pol_stale"] = None  # section 0 of the planes is written here, the rest by the trace of these rays
         d = self._dev
         p = np.asarray(p, dtype=np.float64)
         if Np > N:  # ot_trace walks the whole stride: the padding carries dead rays (weight 0, a valid direction)

@@ -281,9 +281,10 @@ class Raytracer(Group):
         _capi.check(lib.ot_scene_create(C.byref(self._scene.desc), C.byref(handle)))
         self._scene_ref = SceneRef(handle)
         self._scene_handle = handle
-        # Nothing reads the index plane on the way from a trace to an image, a spectrum or a focus: the kernels leave it
-        # unwritten (a sixth of a trace's bytes) and the storage fills it when `n_list` is asked for (RayStorage._ensure_index)
-        _capi.check(lib.ot_scene_set_index_store(handle, 0))
+        # Nothing reads the index plane or the polarisation planes on the way from a trace to an image, a spectrum or a
+        # focus: the kernels leave them unwritten (20 of 48 B per section) and the storage fills them when `n_list` /
+        # `pol_list` is asked for (RayStorage._ensure_index, _ensure_pol)
+        _capi.check(lib.ot_scene_set_deferred_planes(handle, _capi.OT_DEFER_INDEX | _capi.OT_DEFER_POL))
         self._scene_key = key
         return self._scene
 
@@ -420,6 +421,7 @@ class Raytracer(Group):
                 _tail.N, _tail.alive, _tail.traced = int(mb[0]), int(mb[1]), N
             else:
                 rays_obj._index_pending(self._scene_ref, N)
+                rays_obj._pol_pending(self._scene_ref, tab, rng_c, seed, N)
                 _capi.check(lib.ot_generate_and_trace_host(self._scene_handle, tab.handle, rng_c, len(rng_c), seed,
                                                            C.byref(rays), msgs_h.ctypes.data, stream_ptr()))
         else:
@@ -432,6 +434,7 @@ class Raytracer(Group):
                 hn = torch.from_numpy(np.ascontiguousarray(rows).reshape(-1)).to(dev)
             msgs = torch.zeros(n_msgs, dtype=torch.int64, device=dev)
             rays_obj._index_pending(self._scene_ref, rays_obj._Np)  # (ot_trace walks the whole stride)
+            rays_obj._pol_pending(None, None, None, 0, 0)  # (and stores the polarisation planes itself)
             _capi.check(lib.ot_trace(self._scene_handle, C.byref(rays), ptr(hn), seed, ptr(msgs), stream_ptr()))
             msgs_h = msgs.cpu().numpy()  # (synchronises the stream)
 
