@@ -617,6 +617,40 @@ int ot_render_accumulate_compact(int64_t n, const uint32_t* fill, const double* 
 int ot_image_convert(const double* hist, int32_t Nx, int32_t Ny, int32_t fact, int32_t mode, double apx, double K,
                      double L_th, double chroma_scale, double* out, double* workspace, void* stream);
 
+/* ---- colour conversions on arrays of the caller (optrace's color module: xyz.py, luv.py, srgb.py) ---- */
+#define OT_COL_XYZ_TO_XYY 0            /* xyz.py:17   3 -> 3 channels                                              */
+#define OT_COL_XYY_TO_XYZ 1            /* xyz.py:38   3 -> 3                                                       */
+#define OT_COL_XYZ_TO_LUV 2            /* luv.py:20   3 -> 3; OT_IMG_FLAG_NO_NORMALIZE: Yn = 1 instead of max Y    */
+#define OT_COL_LUV_TO_XYZ 3            /* luv.py:74   3 -> 3                                                       */
+#define OT_COL_LUV_TO_UVL 4            /* luv.py:112  3 -> 3                                                       */
+#define OT_COL_LUV_HUE 5               /* luv.py:156  3 -> 1                                                       */
+#define OT_COL_LUV_CHROMA 6            /* luv.py:146  3 -> 1                                                       */
+#define OT_COL_LUV_SATURATION 7        /* luv.py:130  3 -> 1                                                       */
+#define OT_COL_SRGB_LINEAR_TO_XYZ 8    /* srgb.py:50  3 -> 3                                                       */
+#define OT_COL_SRGB_TO_XYZ 9           /* srgb.py:71  3 -> 3                                                       */
+#define OT_COL_XYZ_TO_SRGB_LINEAR 10   /* srgb.py:267 3 -> 3; intent, OT_IMG_FLAG_NO_NORMALIZE, L_th, chroma_scale */
+#define OT_COL_XYZ_TO_SRGB 11          /* srgb.py:379 3 -> 3; the same and OT_IMG_FLAG_NO_CLIP                     */
+#define OT_COL_OUTSIDE_GAMUT 12        /* srgb.py:84  3 -> 1 (1.0 outside, 0.0 inside)                             */
+#define OT_COL_CHROMA_SCALE 13         /* srgb.py:242 Luv -> result[0]; out: NULL or (npx) factors (return_full)   */
+#define OT_COL_LOG_SRGB 14             /* srgb.py:410 3 -> 3; result[0] = 1 where the input came back unchanged    */
+#define OT_COL_SPECTRAL_COLORMAP 15    /* srgb.py:569 in: (npx) wavelengths in nm, out: (npx, 4) sRGB and alpha    */
+
+/* rendering intent, added to OT_COL_XYZ_TO_SRGB_LINEAR / OT_COL_XYZ_TO_SRGB (neither: "Ignore") */
+#define OT_COL_INTENT_ABSOLUTE 0x1000
+#define OT_COL_INTENT_PERCEPTUAL 0x2000
+
+/* One conversion of optrace's color module on a device array: in (npx, 3) float64, pixel after pixel; out (npx, 3) or
+ * (npx) float64 as listed above.  `in` is not modified; out may be `in` for the two XYZ -> sRGB operations only.
+ * L_th and chroma_scale (NaN = automatic) as in ot_image_convert; both are ignored by operations that have no such
+ * argument.  result: host array of one double for OT_COL_CHROMA_SCALE and OT_COL_LOG_SRGB, else it may be NULL.
+ * The image-wide quantities (max Y, the gamut flags, the minimum chroma factor, the lightness range) are maxima,
+ * minima and flags reduced on the device, so no pixel's value depends on its position.  Launches are ordered on
+ * `stream`; the stream is synchronised only where an image-wide decision picks the next launch: once for the Absolute
+ * and twice for the Perceptual intent (as ot_image_convert), once for OT_COL_CHROMA_SCALE, once more for
+ * OT_COL_LOG_SRGB; never for the other operations.  Scratch comes from the library's pool. */
+int ot_color_convert(const double* in, int64_t npx, int32_t op, double L_th, double chroma_scale, double* out,
+                     double* result, void* stream);
+
 /* RenderImage._apply_rayleigh_filter (render_image.py:257-296): out = "same"-size 2-D convolution of each of the
  * 4 channels of `in` (Ny, Nx, 4) with the (2*ps+1)^2 kernel `psf` (device, row-major), zero padded, negative
  * results clamped to 0.  in and out must not alias.  next row, SURVEY 8f rank 2. */

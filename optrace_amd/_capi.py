@@ -176,6 +176,7 @@ SIGNATURES = {
     "ot_scratch_stats": (C.c_int, [C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
     "ot_sphere_projection": (C.c_int, [C.POINTER(Surface), i32, i64, vp, vp, vp]),
     "ot_image_convert": (C.c_int, [vp, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]),
+    "ot_color_convert": (C.c_int, [vp, i64, i32, C.c_double, C.c_double, vp, C.POINTER(C.c_double), vp]),
     "ot_image_convolve": (C.c_int, [vp, i32, i32, vp, i32, vp, vp]),
     "ot_render_accumulate": (C.c_int, [i64, vp, vp, vp, vp, C.POINTER(C.c_double), i32, i32, vp, vp]),
     "ot_render_accumulate_compact": (C.c_int, [i64, vp, vp, vp, vp, vp, C.POINTER(C.c_double), i32, i32, vp, vp]),

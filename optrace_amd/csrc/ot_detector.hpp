@@ -4,8 +4,7 @@
 // misc.py:59-91, color.x/y/z_observer observers.py:14-41).
 // Defines kernels that are no templates: included by ot_detect_api.hip alone (and by the headers of that unit).
 #pragma once
-#include "ot_device.hpp"
-#include "cie_observer_table.inc"
+#include "ot_color_px.hpp"  // observer_xyz_at, the observer table
 
 // Order-preserving map double -> uint64 (and back): min / max of doubles become single hardware integer atomics
 // (global_atomic_umin_x2 / umax_x2) instead of compare-and-swap loops on a plain, possibly stale, load.
@@ -506,27 +505,6 @@ OT_DEV int hit_pixel(const RenderArgs& a, double x, double y, int32_t& ix, int32
     if (x == a.x1) ix = a.Nx - 1;
     if (ix < 0 || iy < 0 || iy >= a.Ny || ix >= a.Nx) return -1;
     return iy * a.Nx + ix;
-}
-
-// color.x/y/z_observer observers.py:14-41 = np.interp on the 1 nm CIE grid: the interval index is floor(wl - 360);
-// obs: the 471 x 3 table (LDS copy)
-OT_DEV void observer_xyz_at(const double* obs, double l, double& xo, double& yo, double& zo) {
-    xo = yo = zo = 0.0;
-    double u = l - OT_OBS_WL0;
-    if (u >= 0.0 && u <= (double)(OT_OBS_N - 1)) {
-        int j = (int)floor(u);
-        if (j >= OT_OBS_N - 1) {
-            xo = obs[3 * (OT_OBS_N - 1)];
-            yo = obs[3 * (OT_OBS_N - 1) + 1];
-            zo = obs[3 * (OT_OBS_N - 1) + 2];
-        } else {
-            double t = l - (OT_OBS_WL0 + (double)j);
-            const double* f0 = &obs[3 * j];
-            xo = (f0[3] - f0[0]) / 1.0 * t + f0[0];
-            yo = (f0[4] - f0[1]) / 1.0 * t + f0[1];
-            zo = (f0[5] - f0[2]) / 1.0 * t + f0[2];
-        }
-    }
 }
 
 // The same from the table of (value, difference) pairs (detector_setup in ot_detect_api.hip: 471 x 6 behind the 471 x 3), for the kernels

@@ -42,7 +42,7 @@ struct Carver {
 OT_INTERNAL int cu_count();  // ot_api.hip
 
 // ---- scratch pool (ot_api.hip, ot_scratch.hpp) ----------------------------------------------------------------------
-enum { OT_WS_RENDER = 0, OT_WS_FUSED = 1, OT_WS_FUSED_HITS = 2, OT_WS_AUTO = 3, OT_WS_DET = 4 };
+enum { OT_WS_RENDER = 0, OT_WS_FUSED = 1, OT_WS_FUSED_HITS = 2, OT_WS_AUTO = 3, OT_WS_DET = 4, OT_WS_COLOR = 5 };
 
 // -> lease on a block of at least `bytes` for this device, stream and purpose; empty when out of memory (the callers fall
 // back to paths without scratch)

@@ -1,16 +1,9 @@
 """Light spectrum presets: CIE standard illuminants, sRGB primary spectra, line combinations (presets/light_spectrum.py)."""
 from __future__ import annotations
 
-import numpy as np
-
 from . import spectral_lines as _lines
 from ..image import SRGB_PRIMARY_POWER_FACTORS, srgb_r_primary, srgb_g_primary, srgb_b_primary
 from ..spectrum import LightSpectrum, illuminant
-
-
-def _equal_energy(wl):
-    """Illuminant E: 100 at every wavelength."""
-    return np.full_like(wl, 100.0, dtype=np.float64)
 
 
 def _srgb_white(wl):
@@ -34,7 +27,7 @@ standard_f: list = []
 standard_led: list = []
 
 for _family, _name in _ILLUMINANTS:
-    _spec = LightSpectrum("Function", func=_equal_energy if _name == "E" else illuminant(_name), desc=_name,
+    _spec = LightSpectrum("Function", func=illuminant(_name), desc=_name,
                           long_desc=f"Illuminant {_name}")
     globals()[_name.lower().replace("-", "_")] = _spec
     globals()[_family].append(_spec)

@@ -28,10 +28,13 @@ def wavelengths(N: int) -> np.ndarray:
 
 
 def illuminant(name: str) -> Callable[[np.ndarray], np.ndarray]:
-    """Linear interpolation of a CIE standard illuminant table (color/illuminants.py:16-...)."""
-    col = _ill_names.index(name)
+    """Linear interpolation of a CIE standard illuminant table (color/illuminants.py:16-...); "E", the equal-energy
+    radiator, is 100 at every wavelength."""
+    col = None if name == "E" else _ill_names.index(name)
 
     def f(wl):
+        if col is None:
+            return np.full_like(wl, 100.0, dtype=np.float64)
         return np.interp(wl, _illuminants[:, 0], _illuminants[:, col], left=0, right=0)
     f.__name__ = f"{name.lower()}_illuminant"
     return f
@@ -313,6 +316,37 @@ class LightSpectrum(Spectrum):
         moment = grid * values
         return float(np.sum((moment[1:] + moment[:-1]) / 2) / np.sum((values[1:] + values[:-1]) / 2))
 
+    def xyz(self) -> np.ndarray:
+        """XYZ colour of the spectrum: the reference's samples and its plain sum (light_spectrum.py:170-194)."""
+        from . import color
+        kind = self.spectrum_type
+        if kind == "Monochromatic":
+            return color.xyz_from_spectrum(np.array([self.wl]), np.array([self.val]))
+        if kind == "Lines":
+            check_type("LightSpectrum.lines", self.lines, (np.ndarray, list))
+            check_type("LightSpectrum.line_vals", self.line_vals, (np.ndarray, list))
+            return color.xyz_from_spectrum(self.lines, self.line_vals)
+        grid = wavelengths(10000 if kind in ("Function", "Data", "Histogram") else 4000)
+        return color.xyz_from_spectrum(grid, self._eval_host(grid))
+
+    def color(self, rendering_intent: str = "Ignore", clip: bool = False, L_th: float = 0.0,
+              chroma_scale: float = 0.0) -> tuple[float, float, float]:
+        """sRGB colour of the spectrum (light_spectrum.py:196-212): `color.xyz_to_srgb` of a 1 x 1 image, on the device."""
+        from . import color
+        rgb = color.xyz_to_srgb(self.xyz().reshape(1, 1, 3), rendering_intent=rendering_intent, clip=clip, L_th=L_th,
+                                chroma_scale=chroma_scale)[0, 0]
+        return float(rgb[0]), float(rgb[1]), float(rgb[2])
+
+    def dominant_wavelength(self) -> float:
+        """Wavelength with the same hue, NaN if there is none (light_spectrum.py:214-220)."""
+        from . import color
+        return float(color.dominant_wavelength(self.xyz()))
+
+    def complementary_wavelength(self) -> float:
+        """Wavelength with the opposite hue, NaN if there is none (light_spectrum.py:222-228)."""
+        from . import color
+        return float(color.complementary_wavelength(self.xyz()))
+
     def fwhm(self) -> float:
         """Full width at half maximum around the highest peak: the nearest crossings of half its height on both sides."""
         kind = self.spectrum_type
@@ -445,6 +479,25 @@ class TransmissionSpectrum(Spectrum):
     def _eval_host(self, wl):
         v = super()._eval_host(wl)
         return v if not self.inverse else 1.0 - v
+
+    def xyz(self) -> np.ndarray:
+        """XYZ colour of the filter under daylight D65 (transmission_spectrum.py:36-45)."""
+        from . import color
+        grid = wavelengths(5000)
+        return color.xyz_from_spectrum(grid, d65_illuminant(grid) * self._eval_host(grid))
+
+    def color(self, rendering_intent="Absolute", clip=True, L_th=0, chroma_scale=None) -> tuple[float, float, float, float]:
+        """sRGB colour and opacity of the filter, all in [0, 1] (transmission_spectrum.py:47-71): the share of daylight
+        that does not pass, gamma-corrected, is the opacity."""
+        from . import color
+        XYZ = self.xyz()
+        grid = wavelengths(5000)
+        Y0 = color.xyz_from_spectrum(grid, d65_illuminant(grid))[1]
+        alpha = (1 - XYZ[1] / Y0) ** (1 / 2.4)
+        XYZ /= Y0
+        rgb = color.xyz_to_srgb(XYZ.reshape(1, 1, 3), rendering_intent=rendering_intent, clip=clip, L_th=L_th,
+                                chroma_scale=chroma_scale)[0, 0]
+        return rgb[0], rgb[1], rgb[2], alpha
 
     def _desc(self, pool: list, lines: np.ndarray | None) -> _capi.Filter:
         """`ot_filter` for this spectrum; tables are appended to `pool`.  `lines` = the distinct f32
