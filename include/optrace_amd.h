@@ -698,6 +698,44 @@ int ot_focus_cost(int64_t count, const double* pasb, const float* w, int32_t mod
                   int32_t n_px, double* workspace, double* cost, void* stream);
 int ot_focus_moments(int64_t count, const double* pasb, const float* w, double b0, double b1, double* sums, void* stream);
 
+/* ---- samplers: optrace/tracer/random.py, Surface.random_positions, color.random_wavelengths_from_srgb ---------
+ * The samplers of the ray generator (ot_rays_generate) as entry points of their own: sample i of a call is what the
+ * generator draws for ray i of a launch with the same seed and the same ranges -- counter-based dither keyed by (seed, i),
+ * strata assigned by a keyed permutation of each range instead of the reference's shuffle (random.py:39-43, 65-66).
+ * `ranges`: the stratification domains, as for ot_rays_generate (`source` and `ray_power` are not read): at most 64 of
+ * them, in order and without gaps over [0, n); each holds at most 2^32 - 1 samples (OT_ERR_UNSUPPORTED beyond).  A range
+ * whose count is a power of two of 4 or more fills a 2^ceil(m/2) x 2^floor(m/2) jittered grid with ALL its samples in the
+ * 2-D samplers; other counts use floor(sqrt(count))^2 cells and draw the rest uniformly, as the reference does.
+ * All outputs are DEVICE arrays of float64; launches are ordered on `stream`; n = 0 returns OT_OK without a launch;
+ * arguments are checked before a device is looked for. */
+#define OT_SAMPLE_INTERVAL 0   /* stratified_interval_sampling random.py:48; bounds = {a, b}; flag: shuffle             */
+#define OT_SAMPLE_RECTANGLE 1  /* stratified_rectangle_sampling random.py:8; bounds = {a, b, c, d}                       */
+#define OT_SAMPLE_RING 2       /* stratified_ring_sampling random.py:70; bounds = {ri, r}; flag: polar                   */
+/* out0[n] and, for the 2-D kinds, out1[n]: x | x, y | x, y or, polar, |r|, theta [rad] (random.py:104-110).  Interval with
+ * flag = 0: stratum i holds sample i of its range (ascending within a range). */
+int ot_sample_stratified(int32_t kind, int32_t flag, const double* bounds, const ot_source_range* ranges, int32_t n_ranges,
+                         uint64_t seed, int64_t n, double* out0, double* out1, void* stream);
+
+/* random_positions of the source shapes (point.py:62, line.py:81, circular_surface.py:33, ring_surface.py:135,
+ * rectangular_surface.py:142): p = x[n] | y[n] | z[n].  Of `shape` only shape, pos, r, ri, dim and angle are read;
+ * OT_SRC_IMAGE_* return OT_ERR_UNSUPPORTED. */
+int ot_sample_positions(const ot_source* shape, const ot_source_range* ranges, int32_t n_ranges, uint64_t seed, int64_t n,
+                        double* p, void* stream);
+
+#define OT_SAMPLE_DISCRETE 0    /* random.py:136-146: entries with f > 0, the first whose running sum reaches X         */
+#define OT_SAMPLE_CONTINUOUS 1  /* random.py:150-157: linear inverse of the cumulative trapezoid                         */
+/* inverse_transform_sampling random.py:113-159 of the pdf f[m] over x[m] (HOST arrays, f >= 0 with a positive sum).
+ * S: DEVICE array of n values in [0, 1], the caller's uniform variable (ranges are not read then), or NULL: n values
+ * stratified over the ranges.  out[n].  The tables go to the device in stream order; the call waits for that copy. */
+int ot_sample_inverse(int32_t kind, const double* x, const double* f, int64_t m, const double* S, int64_t n,
+                      const ot_source_range* ranges, int32_t n_ranges, uint64_t seed, double* out, void* stream);
+
+/* color.random_wavelengths_from_srgb srgb.py:513-553: rgb (n, 3) DEVICE, row-major sRGB values; wl[n] in nm.  The primary
+ * of a row is chosen by a variable stratified over the rows of its range, which, rescaled, also places the wavelength inside
+ * the primary (as for the pixels of an RGB image source); a black row takes the blue primary, as in the reference. */
+int ot_sample_srgb_wavelengths(const double* rgb, int64_t n, const ot_source_range* ranges, int32_t n_ranges, uint64_t seed,
+                               double* wl, void* stream);
+
 /* ---- diagnostics ------------------------------------------------------------------------------------------
  * The tracing loop issues f64 division and square root as their bare cores (reciprocal / reciprocal-square-root seed +
  * the refinement steps of the IEEE sequence, without its range scaling and special-value fix-up; csrc/ot_device.hpp).

@@ -22,6 +22,6 @@ from .raytracer import Raytracer
 from .convolve import convolve
 from .tma import TMA
 from .load import load_agf, load_zmx
-from . import presets, misc, color
+from . import presets, misc, color, random
 
 __version__ = "0.1.0"

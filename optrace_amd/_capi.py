@@ -188,6 +188,11 @@ SIGNATURES = {
     "ot_focus_prepare": (C.c_int, [C.POINTER(Rays), i64, i64, C.c_double, vp, vp, vp, vp]),
     "ot_focus_cost": (C.c_int, [i64, vp, vp, i32, C.POINTER(C.c_double), i32, i32, vp, vp, vp]),
     "ot_focus_moments": (C.c_int, [i64, vp, vp, C.c_double, C.c_double, vp, vp]),
+    "ot_sample_stratified": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(SourceRange), i32, u64, i64, vp, vp, vp]),
+    "ot_sample_positions": (C.c_int, [C.POINTER(Source), C.POINTER(SourceRange), i32, u64, i64, vp, vp]),
+    "ot_sample_inverse": (C.c_int, [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i64, vp, i64, C.POINTER(SourceRange), i32,
+                                    u64, vp, vp]),
+    "ot_sample_srgb_wavelengths": (C.c_int, [vp, i64, C.POINTER(SourceRange), i32, u64, vp, vp]),
     "ot_selftest_arith": (C.c_int, [i32, i32, i64, u64, C.POINTER(i64), C.POINTER(C.c_double), vp]),
     "ot_selftest_eval": (C.c_int, [i32, i64, vp, vp, vp, vp, vp, vp]),
 }
@@ -197,6 +202,8 @@ HIT_PIECES = 1024  # OT_HIT_PIECES
 ABI_VERSION = 9  # OT_ABI_VERSION
 ERR_UNSUPPORTED = -3  # OT_ERR_UNSUPPORTED
 OT_DEFER_INDEX, OT_DEFER_POL = 1, 2  # ot_scene_set_deferred_planes
+SAMPLE_INTERVAL, SAMPLE_RECTANGLE, SAMPLE_RING = range(3)  # OT_SAMPLE_*
+SAMPLE_DISCRETE, SAMPLE_CONTINUOUS = range(2)
 
 _lib = None
 

@@ -1,6 +1,7 @@
 """Colour conversions and colour figures: mirror of optrace/tracer/color (xyz.py, luv.py, srgb.py, observers.py, tools.py,
-illuminants.py), every name but `random_wavelengths_from_srgb` (wavelengths of RGB pixels are drawn inside the
-generation kernel).
+illuminants.py), every name but `random_wavelengths_from_srgb`: that one lives in `optrace_amd.random`
+(`ot.random.random_wavelengths_from_srgb`), beside the samplers it is built from; the wavelengths of the pixels of an RGB
+image source are drawn by the same arithmetic inside the generation kernel.
 
 Two halves.  Tables and scalar figures (observers, illuminants, blackbody, `xyz_from_spectrum`, dominant and
 complementary wavelength, the gamma curves of `image.py`) are NumPy on the host and need no GPU.  The per-pixel

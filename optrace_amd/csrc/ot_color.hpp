@@ -15,13 +15,6 @@
 #define OT_CRED_LPMAX 10    // max L | L > 0                          srgb.py:428
 #define OT_CRED_N 16
 
-OT_DEV double srgb_inverse_gamma(double v) {  // srgb_to_srgb_linear srgb.py:30-47
-    double a = 0.055, av = fabs(v);
-    if (av <= 0.04045) return 1 / 12.92 * v;
-    double sg = (v > 0) - (v < 0);
-    return sg * pow(1 / (1 + a) * (av + a), 2.4);
-}
-
 OT_DEV void rgbl_to_xyz1(double r, double g, double b, double& X, double& Y, double& Z) {  // srgb_linear_to_xyz srgb.py:50-68
     X = 0.4124564 * r + 0.3575761 * g + 0.1804375 * b;
     Y = 0.2126729 * r + 0.7151522 * g + 0.0721750 * b;

@@ -75,6 +75,13 @@ OT_DEV double srgb_gamma(double v) {  // srgb_linear_to_srgb srgb.py:358-376
     return sg * ((1 + a) * pow(av, 1 / 2.4) - a);
 }
 
+OT_DEV double srgb_inverse_gamma(double v) {  // srgb_to_srgb_linear srgb.py:30-47
+    double a = 0.055, av = fabs(v);
+    if (av <= 0.04045) return 1 / 12.92 * v;
+    double sg = (v > 0) - (v < 0);
+    return sg * pow(1 / (1 + a) * (av + a), 2.4);
+}
+
 OT_DEV void wave_atomic_max(double* addr, double v) {  // NaN-ignoring maximum (np.nanmax)
     double m = wave_max(isnan(v) ? -__builtin_inf() : v);
     if (__lane_id() == 0 && m > -__builtin_inf()) atomic_max_f64(addr, m);

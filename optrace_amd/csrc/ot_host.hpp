@@ -42,7 +42,7 @@ struct Carver {
 OT_INTERNAL int cu_count();  // ot_api.hip
 
 // ---- scratch pool (ot_api.hip, ot_scratch.hpp) ----------------------------------------------------------------------
-enum { OT_WS_RENDER = 0, OT_WS_FUSED = 1, OT_WS_FUSED_HITS = 2, OT_WS_AUTO = 3, OT_WS_DET = 4, OT_WS_COLOR = 5 };
+enum { OT_WS_RENDER = 0, OT_WS_FUSED = 1, OT_WS_FUSED_HITS = 2, OT_WS_AUTO = 3, OT_WS_DET = 4, OT_WS_COLOR = 5, OT_WS_SAMPLE = 6 };
 
 // -> lease on a block of at least `bytes` for this device, stream and purpose; empty when out of memory (the callers fall
 // back to paths without scratch)
@@ -79,3 +79,17 @@ OT_INTERNAL void drop_range_cache(ot_sources* s);
 // the source table's cache until a different list arrives).
 OT_INTERNAL int make_ranges(const ot_source_range* ranges, int32_t n_ranges, const ot_sources* src_c, int64_t N,
                             const RangeArgs** out);
+
+// The argument block of a sampler kernel (ot_sample_api.hip): the same per-range constants, for ranges that belong to no
+// source table -- at most OT_MAX_RANGES of them, in order and gap-free over [0, N); nothing goes to device memory.  `who`
+// names the entry point in the messages.
+OT_INTERNAL int sampler_ranges(const char* who, const ot_source_range* ranges, int32_t n_ranges, int64_t N, RangeArgs* out);
+
+// ---- inverse-CDF tables (ot_sources_api.hip) ------------------------------------------------------------------------
+// Start hints (CdfGuide, ot_scene.hpp) for the cumulative table F[n] searched over [x0, F[n - 1]]: fills dst->K, x0 and
+// scale and appends the K bucket entries to `guides`; -> their offset in `guides` (dst->g is the caller's to set once the
+// entries have an address on the device).
+OT_INTERNAL size_t build_cdf_guide(const double* F, size_t n, double x0, CdfGuide* dst, std::vector<int32_t>& guides);
+
+// The inverse cumulative spectra of the three sRGB primaries, 3 x (OT_PRIM_M + 1) nodes (SourceDev::prim_inv).
+OT_INTERNAL const std::vector<double>& srgb_primary_inverse_tables();

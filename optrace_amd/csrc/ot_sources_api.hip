@@ -33,6 +33,56 @@ static double srgb_to_linear(double v) {  // color/srgb.py:30-47
     return sg * std::pow(1 / (1 + a) * (av + a), 2.4);
 }
 
+// ot_host.hpp: start hints of an inverse-CDF search, ~4 buckets per table node
+size_t build_cdf_guide(const double* F, size_t n, double x0, CdfGuide* dst, std::vector<int32_t>& guides) {
+    const double x1 = F[n - 1];
+    size_t K = 16;
+    while (K < 4 * n && K < ((size_t)1 << 22)) K <<= 1;  // ~4 buckets per table node
+    dst->K = (int32_t)K;
+    dst->x0 = x0;
+    dst->scale = (x1 > x0) ? (double)K / (x1 - x0) : 0.0;
+    const size_t off = guides.size();
+    size_t j = 0;
+    for (size_t b = 0; b < K; b++) {
+        const double xb = x0 + (double)b / (dst->scale > 0 ? dst->scale : 1.0);
+        while (j + 1 < n && F[j + 1] <= xb) j++;
+        guides.push_back((int32_t)j);
+    }
+    return off;
+}
+
+// ot_host.hpp: SourceDev::prim_inv, built once per process
+const std::vector<double>& srgb_primary_inverse_tables() {
+    // The three primaries over wavelengths(5000) (srgb.py:528, 549-551): cumulative trapezoid F_j, and the inverse
+    // x(F) the reference interpolates linearly between its nodes (random.py:150-157) sampled at OT_PRIM_M + 1
+    // equidistant values of the uniform variable.  Between two samples the device interpolates linearly as well:
+    // exact where no node lies between them, elsewhere off by less than the spacing of the reference's own
+    // wavelength grid (0.08 nm) except in the few buckets of the far tails (1.5e-5 of the rays each).
+    static const std::vector<double> tables = [] {
+        std::vector<double> inv(3 * (size_t)(OT_PRIM_M + 1));
+        std::vector<double> x(OT_PRIM_N), F(OT_PRIM_N);
+        for (int c = 0; c < 3; c++) {
+            double prev = 0.0;
+            for (int j = 0; j < OT_PRIM_N; j++) {
+                x[j] = 380.0 + (780.0 - 380.0) * (double)j / (double)(OT_PRIM_N - 1);
+                double f = srgb_primary(c, x[j]);
+                F[j] = (j == 0) ? 0.0 : F[j - 1] + (f + prev) / 2;
+                prev = f;
+            }
+            double* o = inv.data() + (size_t)c * (OT_PRIM_M + 1);
+            int lo = 0;
+            for (int m = 0; m <= OT_PRIM_M; m++) {
+                const double X = F[0] + ((double)m / (double)OT_PRIM_M) * (F[OT_PRIM_N - 1] - F[0]);
+                while (lo < OT_PRIM_N - 2 && F[lo + 1] <= X) lo++;
+                const double dF = F[lo + 1] - F[lo];
+                o[m] = (dF > 0) ? x[lo] + (X - F[lo]) / dF * (x[lo + 1] - x[lo]) : x[lo];
+            }
+        }
+        return inv;
+    }();
+    return tables;
+}
+
 extern "C" int ot_sources_create(const ot_source* sources, int32_t n_sources, ot_sources** out) {
     if (!sources || !out || n_sources < 1) return fail(OT_ERR_INVALID, "ot_sources_create: bad argument");
     if (int rc = require_device()) return rc;
@@ -58,19 +108,7 @@ extern "C" int ot_sources_create(const ot_source* sources, int32_t n_sources, ot
     struct GuideRef { size_t off; CdfGuide* dst; };
     std::vector<GuideRef> grefs;
     auto add_guide = [&](const double* F, size_t n, double x0, CdfGuide* dst) {
-        const double x1 = F[n - 1];
-        size_t K = 16;
-        while (K < 4 * n && K < ((size_t)1 << 22)) K <<= 1;  // ~4 buckets per table node
-        dst->K = (int32_t)K;
-        dst->x0 = x0;
-        dst->scale = (x1 > x0) ? (double)K / (x1 - x0) : 0.0;
-        grefs.push_back({guides.size(), dst});
-        size_t j = 0;
-        for (size_t b = 0; b < K; b++) {
-            const double xb = x0 + (double)b / (dst->scale > 0 ? dst->scale : 1.0);
-            while (j + 1 < n && F[j + 1] <= xb) j++;
-            guides.push_back((int32_t)j);
-        }
+        grefs.push_back({build_cdf_guide(F, n, x0, dst, guides), dst});
     };
     struct PickRef { size_t off; int src; };
     std::vector<PickRef> pick_refs;
@@ -189,30 +227,7 @@ extern "C" int ot_sources_create(const ot_source* sources, int32_t n_sources, ot
     }
     size_t prim_off = (size_t)-1;
     if (any_rgb) {
-        // The three primaries over wavelengths(5000) (srgb.py:528, 549-551): cumulative trapezoid F_j, and the inverse
-        // x(F) the reference interpolates linearly between its nodes (random.py:150-157) sampled at OT_PRIM_M + 1
-        // equidistant values of the uniform variable.  Between two samples the device interpolates linearly as well:
-        // exact where no node lies between them, elsewhere off by less than the spacing of the reference's own
-        // wavelength grid (0.08 nm) except in the few buckets of the far tails (1.5e-5 of the rays each).
-        std::vector<double> inv(3 * (size_t)(OT_PRIM_M + 1));
-        std::vector<double> x(OT_PRIM_N), F(OT_PRIM_N);
-        for (int c = 0; c < 3; c++) {
-            double prev = 0.0;
-            for (int j = 0; j < OT_PRIM_N; j++) {
-                x[j] = 380.0 + (780.0 - 380.0) * (double)j / (double)(OT_PRIM_N - 1);
-                double f = srgb_primary(c, x[j]);
-                F[j] = (j == 0) ? 0.0 : F[j - 1] + (f + prev) / 2;
-                prev = f;
-            }
-            double* o = inv.data() + (size_t)c * (OT_PRIM_M + 1);
-            int lo = 0;
-            for (int m = 0; m <= OT_PRIM_M; m++) {
-                const double X = F[0] + ((double)m / (double)OT_PRIM_M) * (F[OT_PRIM_N - 1] - F[0]);
-                while (lo < OT_PRIM_N - 2 && F[lo + 1] <= X) lo++;
-                const double dF = F[lo + 1] - F[lo];
-                o[m] = (dF > 0) ? x[lo] + (X - F[lo]) / dF * (x[lo + 1] - x[lo]) : x[lo];
-            }
-        }
+        const std::vector<double>& inv = srgb_primary_inverse_tables();
         prim_off = push(inv.data(), inv.size());
     }
 
@@ -258,6 +273,39 @@ extern "C" int ot_sources_create(const ot_source* sources, int32_t n_sources, ot
     }
     (void)hipGetDevice(&so->device);
     *out = so;
+    return OT_OK;
+}
+
+// per-range constants of the stratified samplers: floor(sqrt(count)), 1 / count and 1 / floor(sqrt(count))
+static void range_constants(uint64_t cnt, uint32_t& n2, double& inv_n, double& inv_n2) {
+    n2 = (uint32_t)std::sqrt((double)cnt);
+    while ((uint64_t)n2 * n2 > cnt) n2--;
+    while ((uint64_t)(n2 + 1) * (n2 + 1) <= cnt) n2++;
+    inv_n = cnt ? 1.0 / (double)cnt : 0.0;
+    inv_n2 = n2 ? 1.0 / (double)n2 : 0.0;
+}
+
+// ot_host.hpp: the argument block of the sampler kernels (ot_sample_api.hip) -- no source table behind the ranges, no cache
+int sampler_ranges(const char* who, const ot_source_range* ranges, int32_t n_ranges, int64_t N, RangeArgs* out) {
+    const std::string w(who);
+    if (!ranges || n_ranges < 1) return fail(OT_ERR_INVALID, w + ": at least one range is needed");
+    if (n_ranges > OT_MAX_RANGES) return fail(OT_ERR_UNSUPPORTED, w + ": more than 64 ranges");
+    RangeArgs& rg = *out;
+    rg.ext = nullptr;
+    rg.n = n_ranges;
+    int64_t covered = 0;
+    for (int q = 0; q < n_ranges; q++) {
+        if (ranges[q].first < 0 || ranges[q].count < 0) return fail(OT_ERR_INVALID, w + ": negative range");
+        if (ranges[q].count > 0xffffffffll) return fail(OT_ERR_UNSUPPORTED, w + ": more than 2^32 - 1 samples in one range");
+        if (ranges[q].first != covered) return fail(OT_ERR_INVALID, w + ": the ranges must cover all samples once, in order");
+        range_constants((uint64_t)ranges[q].count, rg.n2[q], rg.inv_n[q], rg.inv_n2[q]);
+        rg.w[q] = 0.0f;
+        rg.source[q] = 0;
+        rg.first[q] = ranges[q].first;
+        rg.count[q] = ranges[q].count;
+        covered += ranges[q].count;
+    }
+    if (covered != N) return fail(OT_ERR_INVALID, w + ": the ranges must cover all samples once, in order");
     return OT_OK;
 }
 
@@ -311,10 +359,9 @@ int make_ranges(const ot_source_range* ranges, int32_t n_ranges, const ot_source
             return fail(OT_ERR_INVALID, "range: ray count differs from the length of the source's orientation array");
         if (ranges[k].first != covered) return fail(OT_ERR_INVALID, "source ranges must cover all N rays exactly once");
         const uint64_t cnt = (uint64_t)ranges[k].count;
-        uint32_t n2 = (uint32_t)std::sqrt((double)cnt);
-        while ((uint64_t)n2 * n2 > cnt) n2--;
-        while ((uint64_t)(n2 + 1) * (n2 + 1) <= cnt) n2++;
-        const double inv_n = cnt ? 1.0 / (double)cnt : 0.0, inv_n2 = n2 ? 1.0 / (double)n2 : 0.0;
+        uint32_t n2;
+        double inv_n, inv_n2;
+        range_constants(cnt, n2, inv_n, inv_n2);
         const float w = (float)(ranges[k].ray_power > 0 ? ranges[k].ray_power
                                                         : (cnt ? src->power[ranges[k].source] / (double)cnt : 0.0));
         if (big) {

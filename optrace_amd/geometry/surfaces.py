@@ -234,6 +234,12 @@ class CircularSurface(Surface):
         self._set_flat()
         self.lock()
 
+    def random_positions(self, N: int, *, seed: int = None) -> np.ndarray:
+        """(N, 3) float64, Fortran order: random positions on the disc (circular_surface.py:33-44), stratified -- the start
+        positions the ray generator gives N rays of a source with this shape and the same seed (`ot.random`)."""
+        from ..random import shape_positions
+        return shape_positions({"shape": _capi.SRC_CIRCLE, "pos": [float(v) for v in self.pos], "r": float(self.r)}, N, seed)
+
 
 class RingSurface(Surface):
     """Flat annulus r_i <= r <= r_o (ring_surface.py:10-161)."""
@@ -257,6 +263,13 @@ class RingSurface(Surface):
     def _mask_host(self, x, y):
         rr = (x - self.pos[0]) ** 2 + (y - self.pos[1]) ** 2
         return (rr >= (self.ri - self.N_EPS) ** 2) & Surface._mask_host(self, x, y)
+
+    def random_positions(self, N: int, *, seed: int = None) -> np.ndarray:
+        """(N, 3) float64, Fortran order: random positions on the annulus (ring_surface.py:135-149), stratified -- the start
+        positions the ray generator gives N rays of a source with this shape and the same seed (`ot.random`)."""
+        from ..random import shape_positions
+        return shape_positions({"shape": _capi.SRC_RING, "pos": [float(v) for v in self.pos], "r": float(self.r),
+                                "ri": float(self.ri)}, N, seed)
 
     def _desc(self):
         d = Surface._desc(self)
@@ -323,6 +336,13 @@ class RectangularSurface(Surface):
 
     def _mask_host(self, x, y):
         return self._in_rect(x, y, self.dim / 2, self.N_EPS)
+
+    def random_positions(self, N: int, *, seed: int = None) -> np.ndarray:
+        """(N, 3) float64, Fortran order: random positions on the rotated rectangle (rectangular_surface.py:142-160), stratified -- the start
+        positions the ray generator gives N rays of a source with this shape and the same seed (`ot.random`)."""
+        from ..random import shape_positions
+        return shape_positions({"shape": _capi.SRC_RECT, "pos": [float(v) for v in self.pos],
+                                "dim": [float(self.dim[0]), float(self.dim[1])], "angle": float(self._angle)}, N, seed)
 
     def _desc(self):
         d = Surface._desc(self)
@@ -527,6 +547,12 @@ class Point(_Shape):
         x, y, z = self.pos
         return x, x, y, y, z, z
 
+    def random_positions(self, N: int, *, seed: int = None) -> np.ndarray:
+        """(N, 3) float64, Fortran order: random positions of the point: its position, N times (point.py:62-69), stratified -- the start
+        positions the ray generator gives N rays of a source with this shape and the same seed (`ot.random`)."""
+        from ..random import shape_positions
+        return shape_positions({"shape": _capi.SRC_POINT, "pos": [float(v) for v in self.pos]}, N, seed)
+
 
 class Line(_Shape):
     """Line source shape in the xy plane (line.py:9-112)."""
@@ -550,6 +576,13 @@ class Line(_Shape):
         x, y, z = self.pos
         hx, hy = self.r * np.cos(np.deg2rad(self.angle)), self.r * np.sin(np.deg2rad(self.angle))
         return x - hx, x + hx, y - hy, y + hy, z, z
+
+    def random_positions(self, N: int, *, seed: int = None) -> np.ndarray:
+        """(N, 3) float64, Fortran order: random positions on the line (line.py:81-96), stratified -- the start
+        positions the ray generator gives N rays of a source with this shape and the same seed (`ot.random`)."""
+        from ..random import shape_positions
+        return shape_positions({"shape": _capi.SRC_LINE, "pos": [float(v) for v in self.pos], "r": float(self.r),
+                                "angle": float(np.deg2rad(self.angle))}, N, seed)
 
     def __setattr__(self, key, val):
         if key in ("r", "angle"):

@@ -20,6 +20,24 @@ from ._warn import warning
 from . import misc
 
 
+MIN_BLOCK = 1 << 16  # blocks below this size are not cut further (their share of the rays, and of the time, is negligible)
+
+
+def stratification_blocks(first: int, n: int, max_blocks: int) -> list:
+    """[(first, count), ...]: the stratification ranges of `n` samples starting at `first` -- power-of-two blocks from
+    MIN_BLOCK on, largest first, plus one ragged rest; at most `max_blocks` of them.  A power-of-two block's stratum
+    permutation needs no rejection step (ot_generate.hpp::permute_index), and a wave runs as long as its slowest lane.
+    The one cutting rule of the rays of a source (`RayStorage._source_ranges`) and of the samples of `ot.random`: equal
+    (seed, n) give equal draws in both."""
+    blocks, rest = [], int(n)
+    while rest >= MIN_BLOCK and rest & (rest - 1) and len(blocks) < max_blocks - 1:
+        blk = 1 << (rest.bit_length() - 1)
+        blocks.append((first, blk))
+        first, rest = first + blk, rest - blk
+    blocks.append((first, rest))
+    return blocks
+
+
 class SourceTable:
     """Device copy of the `ot_source` table of a list of RaySources (handle from ot_sources_create)."""
 
@@ -347,28 +365,22 @@ class RayStorage(BaseClass):
                                                           C.byref(self._rays_struct()), 0, count, stream_ptr()))
         self.__dict__["_pol_stale"] = None  # (after the launch: a call that fails leaves the planes marked)
 
-    # blocks below this size are not cut further (their share of the rays, and of the time, is negligible)
-    _MIN_BLOCK = 1 << 16
+    _MIN_BLOCK = MIN_BLOCK
 
     def _source_ranges(self):
         """Stratification ranges of the launch.  The reference cuts every source's rays among its threads and each
         thread stratifies its own share (ray_storage.py:147-166); here a source's rays are cut into power-of-two
-        blocks, largest first, plus one ragged rest: a power-of-two block's stratum permutation needs no rejection
-        step (ot_generate.hpp::permute_index), and a wave runs as long as its slowest lane.  Every ray of a source
-        carries power / N_source, whatever its block."""
+        blocks, largest first, plus one ragged rest (`stratification_blocks`).  Every ray of a source carries
+        power / N_source, whatever its block."""
         if self._ranges is not None:
             return self._ranges
         per_source = max(1, 64 // max(len(self.N_list), 1))  # at most 64 ranges travel as kernel arguments
         recs = []
         for i, n in enumerate(int(v) for v in self.N_list):
-            first, rest = int(self.B_list[i]), n
             ray_power = self._powers[i] / n if n else 0.
-            if self.ray_source_list[i].orientation != "Function":  # those read one orientation array per range
-                while rest >= self._MIN_BLOCK and rest & (rest - 1) and sum(r[0] == i for r in recs) < per_source - 1:
-                    blk = 1 << (rest.bit_length() - 1)
-                    recs.append((i, first, blk, ray_power))
-                    first, rest = first + blk, rest - blk
-            recs.append((i, first, rest, ray_power))
+            # (sources with a function orientation read one orientation array per range: uncut)
+            cut = per_source if self.ray_source_list[i].orientation != "Function" else 1
+            recs += [(i, first, count, ray_power) for first, count in stratification_blocks(int(self.B_list[i]), n, cut)]
         rng = (_capi.SourceRange * len(recs))()
         for r, (i, first, count, ray_power) in zip(rng, recs):
             r.source, r.first, r.count, r.ray_power = i, first, count, ray_power
