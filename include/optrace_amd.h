@@ -698,6 +698,34 @@ int ot_focus_cost(int64_t count, const double* pasb, const float* w, int32_t mod
                   int32_t n_px, double* workspace, double* cost, void* stream);
 int ot_focus_moments(int64_t count, const double* pasb, const float* w, double b0, double b1, double* sums, void* stream);
 
+/* ---- spot analysis (Raytracer.spot_analysis; no counterpart in optrace) ----------------------------------------
+ * Figures of the hits of one detector, from the hit list of ot_detector_hits_multi: x[], y[] (f64 planes of ph), w[] (f32),
+ * all DEVICE.  fill = NULL: a dense list of n entries; otherwise the compact list of a bundle of n rays
+ * (ot_detector_req.fill: piece k contributes its first fill[k] entries).  An entry counts when w > 0; positions of the
+ * others are not read into arithmetic.  Launches are ordered on `stream` and nothing is waited for: each call reads what
+ * the one before it left in device memory.  Null arguments (fill apart): OT_ERR_INVALID, limits exceeded:
+ * OT_ERR_UNSUPPORTED, both before a device is looked for; n = 0 returns OT_OK without a launch and leaves the outputs alone.
+ * ot_spot_moments: moments[OT_SPOT_M] (device) = sum w | sum w x | sum w y | number of hits | sum w dx^2 | sum w dy^2 |
+ *   sum w dx dy | max (dx^2 + dy^2), with d = p - c formed before squaring, c = (sum w x, sum w y) / sum w: a second pass
+ *   over the list.  All zero without a hit.  workspace (device) >= OT_SPOT_WS(0) doubles.
+ * ot_spot_radial: hist[n_radii] (device, f64, accumulated into: zero it first) += w per bin
+ *   min(floor(r / r_max * n_radii), n_radii - 1), r = sqrt(dx^2 + dy^2), r_max = sqrt(moments[7]); bin 0 when r_max = 0.
+ *   1 <= n_radii <= OT_SPOT_MAX_RADII.  The one call whose sums depend on the order of arrival (f64 atomics).
+ * ot_spot_otf: otf[4 * K] (device) = re x | im x | re y | im y of sum w exp(-2 pi i freq[k] d) per axis, freq[K] (device)
+ *   in cycles per length unit, 1 <= K <= OT_SPOT_MAX_FREQ; workspace (device) >= OT_SPOT_WS(K) doubles.
+ * ot_spot_moments and ot_spot_otf add in an order fixed by n, K and the kind of list: the same call returns the same bits. */
+#define OT_SPOT_M 8
+#define OT_SPOT_MAX_RADII 65536
+#define OT_SPOT_MAX_FREQ 4096
+#define OT_SPOT_BLOCKS 2048 /* most workgroups whose partial sums the workspace holds */
+#define OT_SPOT_WS(K) (32 * OT_SPOT_BLOCKS + 256 * ((K) + 8))
+int ot_spot_moments(int64_t n, const uint32_t* fill, const double* x, const double* y, const float* w, double* workspace,
+                    double* moments, void* stream);
+int ot_spot_radial(int64_t n, const uint32_t* fill, const double* x, const double* y, const float* w, const double* moments,
+                   int32_t n_radii, double* hist, void* stream);
+int ot_spot_otf(int64_t n, const uint32_t* fill, const double* x, const double* y, const float* w, const double* moments,
+                const double* freq, int32_t K, double* workspace, double* otf, void* stream);
+
 /* ---- samplers: optrace/tracer/random.py, Surface.random_positions, color.random_wavelengths_from_srgb ---------
  * The samplers of the ray generator (ot_rays_generate) as entry points of their own: sample i of a call is what the
  * generator draws for ray i of a launch with the same seed and the same ranges -- counter-based dither keyed by (seed, i),

@@ -17,6 +17,7 @@ from .geometry import (Surface, CircularSurface, RingSurface, RectangularSurface
                        FunctionSurface1D, FunctionSurface2D, PointMarker, LineMarker)
 from .image import RGBImage, GrayscaleImage, ScalarImage
 from .render_image import RenderImage
+from .spot import SpotAnalysis
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
 from .convolve import convolve

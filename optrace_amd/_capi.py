@@ -188,6 +188,9 @@ SIGNATURES = {
     "ot_focus_prepare": (C.c_int, [C.POINTER(Rays), i64, i64, C.c_double, vp, vp, vp, vp]),
     "ot_focus_cost": (C.c_int, [i64, vp, vp, i32, C.POINTER(C.c_double), i32, i32, vp, vp, vp]),
     "ot_focus_moments": (C.c_int, [i64, vp, vp, C.c_double, C.c_double, vp, vp]),
+    "ot_spot_moments": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, vp]),
+    "ot_spot_radial": (C.c_int, [i64, vp, vp, vp, vp, vp, i32, vp, vp]),
+    "ot_spot_otf": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
     "ot_sample_stratified": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(SourceRange), i32, u64, i64, vp, vp, vp]),
     "ot_sample_positions": (C.c_int, [C.POINTER(Source), C.POINTER(SourceRange), i32, u64, i64, vp, vp]),
     "ot_sample_inverse": (C.c_int, [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i64, vp, i64, C.POINTER(SourceRange), i32,
@@ -204,6 +207,12 @@ ERR_UNSUPPORTED = -3  # OT_ERR_UNSUPPORTED
 OT_DEFER_INDEX, OT_DEFER_POL = 1, 2  # ot_scene_set_deferred_planes
 SAMPLE_INTERVAL, SAMPLE_RECTANGLE, SAMPLE_RING = range(3)  # OT_SAMPLE_*
 SAMPLE_DISCRETE, SAMPLE_CONTINUOUS = range(2)
+SPOT_M, SPOT_MAX_RADII, SPOT_MAX_FREQ = 8, 65536, 4096  # OT_SPOT_*
+
+
+def spot_ws(K: int) -> int:
+    """OT_SPOT_WS(K): doubles of workspace for ot_spot_moments (K = 0) and ot_spot_otf."""
+    return 32 * 2048 + 256 * (K + 8)
 
 _lib = None
 

@@ -5,6 +5,7 @@
 // Defines kernels that are no templates: included by ot_detect_api.hip alone (and by the headers of that unit).
 #pragma once
 #include "ot_color_px.hpp"  // observer_xyz_at, the observer table
+#include "ot_hit_list.hpp"  // OT_HIT_PIECES_N, hit_piece_shift / hit_piece_len
 
 // Order-preserving map double -> uint64 (and back): min / max of doubles become single hardware integer atomics
 // (global_atomic_umin_x2 / umax_x2) instead of compare-and-swap loops on a plain, possibly stale, load.
@@ -148,16 +149,6 @@ struct DetOne {
     unsigned int* fill;
     int piece_shift;
 };
-
-#define OT_HIT_PIECES_N 1024
-// entries per piece of a compact hit list of capacity n: the power of two at or above n / 1024 (at least 1024), so that a
-// ray's piece is a shift of its index; the last pieces of the 1024 stay empty
-__host__ __device__ static inline int hit_piece_shift(int64_t n) {
-    int s = 10;
-    while (((int64_t)OT_HIT_PIECES_N << s) < n) s++;
-    return s;
-}
-__host__ __device__ static inline int64_t hit_piece_len(int64_t n) { return (int64_t)1 << hit_piece_shift(n); }
 
 // Raytracer._hit_detector raytracer.py:922-1051, one lane per ray of [first, first+count), n_det detectors.
 // ill[0] += ill-conditioned rays, ill[1] += rays whose numeric hit search timed out.

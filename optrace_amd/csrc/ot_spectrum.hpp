@@ -8,40 +8,18 @@
 #pragma once
 #include "ot_detector.hpp"
 #include "ot_device.hpp"
-
-#define OT_SPEC_SLICE 8192  // entries of a compact list a workgroup takes at a time
+#include "ot_hit_list.hpp"
 
 // pass 1: wavelength range and number of selected rays.  stats = {min wl, max wl} (pre-set to +inf / -inf),
 // count[0] += rays with w > 0 (np.count_nonzero(w) over the selected rays, light_spectrum.py:60,70)
-// index walk shared by both passes: dense = grid-stride over [0, n); compact = the workgroup takes whole pieces
-template <class F>
-OT_DEV void spectrum_for_each(int64_t n, const unsigned int* __restrict__ fill, F&& body) {
-    if (!fill) {
-        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) body(i);
-        return;
-    }
-    // work items = (piece, slice of OT_SPEC_SLICE entries): a workgroup per whole piece left the 1024 pieces of a long list
-    // (2e8 rays: 7e4 filled entries each) to 1024 workgroups walking them serially -- 0.54 / 0.84 ms for the two passes
-    // over 0.56 GB; slices beyond a piece's fill cost one comparison
-    const int shift = hit_piece_shift(n);
-    const int64_t slices = (((int64_t)1 << shift) + OT_SPEC_SLICE - 1) / OT_SPEC_SLICE;  // per piece
-    for (int64_t it = blockIdx.x; it < OT_HIT_PIECES_N * slices; it += gridDim.x) {
-        const int64_t sl = it / OT_HIT_PIECES_N, pc = it % OT_HIT_PIECES_N;  // slice-major: the filled front slices spread over all workgroups
-        const int64_t i0 = (pc << shift) + sl * OT_SPEC_SLICE;
-        int64_t i1 = (pc << shift) + (int64_t)fill[pc];
-        if (i1 > i0 + OT_SPEC_SLICE) i1 = i0 + OT_SPEC_SLICE;
-        for (int64_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) body(i);
-    }
-}
-
+// index walk shared by both passes: hit_list_for_each (ot_hit_list.hpp)
 __global__ __launch_bounds__(256) void spectrum_stats_kernel(int64_t n, const float* __restrict__ wl, const float* __restrict__ w,
                                                              double* __restrict__ stats, unsigned long long* __restrict__ count,
                                                              const unsigned int* __restrict__ fill) {
     const double inf = __builtin_inf();
     double lo = inf, hi = -inf;
     unsigned long long c = 0;
-    spectrum_for_each(n, fill, [&](int64_t i) {
+    hit_list_for_each(n, fill, [&](int64_t i) {
         if (w[i] > 0.f) {
             double l = (double)wl[i];
             lo = fmin(lo, l);
@@ -78,7 +56,7 @@ __global__ __launch_bounds__(1024) void spectrum_hist_kernel(int64_t n, const fl
     const float first = edges[0], last = edges[nbins];
     const float denom = last - first;
     const float fn = (float)nbins;
-    spectrum_for_each(n, fill, [&](int64_t i) {
+    hit_list_for_each(n, fill, [&](int64_t i) {
         float wi = w[i];
         if (!(wi > 0.f)) return;
         float x = wl[i];

@@ -31,6 +31,8 @@ from .ray_storage import RayStorage, TailStorage, SceneRef
 from .refraction_index import RefractionIndex
 from .render_image import RenderImage
 from .spectrum import LightSpectrum
+from . import spot as _spot
+from .spot import SpotAnalysis
 from .geometry.ray_source import RaySource
 from .scene import CompiledScene, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
@@ -838,6 +840,26 @@ class Raytracer(Group):
         spec = LightSpectrum.render(wl, w, long_desc=prefix + self._detector_label(detector_index), **kwargs)
         self._warn_ill(ill_count, detector_index)
         return spec
+
+    def spot_analysis(self, detector_index: int = 0, source_index: int = None, extent=None,
+                      projection_method: str = "Equidistant", n_radii: int = 256, frequencies=None) -> SpotAnalysis:
+        """Centroid, RMS size, encircled energy and geometric MTF of the hits on a detector (no counterpart in optrace):
+        hit search as for `detector_image`, then reductions over the hit list on the GPU (spot.py).  n_radii: radial bins of
+        the encircled energy; frequencies: where the transfer function is wanted, in cycles per length unit (default: 65
+        values up to 1 / RMS radius)."""
+        freq = _spot.check_arguments(n_radii, frequencies)
+        require_device()  # (said before anything about the rays: without a device there are none)
+        # (long bundles: the list of the valid hits only, as for the detector image)
+        spec = dict(detector_index=detector_index, source_index=source_index, extent=extent,
+                    projection_method=projection_method, compact=self.rays.N >= self.COMPACT_HITS_FROM)
+        xy, w, wl, extent_out, _, ill_count, label = self._hit_detectors("Spot Analysis", [spec])[0]
+        fill = wl[1] if isinstance(wl, tuple) else None  # compact hit list: (wavelengths, fill counts)
+        if source_index is not None:
+            label = f"Rays from RS{source_index} at {label}"
+        first, end = self._ray_range(source_index)
+        sa = _spot.analyse(xy, w, end - first, fill, extent_out, n_radii, freq, long_desc="Spot at " + label)
+        self._warn_ill(ill_count, detector_index)
+        return sa
 
     # ---- source side (raytracer.py:1281-1352) ---------------------------------------------------------------
     def _hit_source(self, info: str, source_index: int = 0):
