@@ -681,7 +681,9 @@ int ot_spectrum_histogram_compact(int64_t n, const uint32_t* fill, const float* 
  *   without such a section; n_use[0] (device) = number of rays kept.
  * ot_focus_cost: cost function __focus_search_cost_function (raytracer.py:1354-1418) of the kept rays at the nz
  *   positions z[] (host array), mode OT_FOCUS_*; cost[nz] (device).  n_px = image side for the image methods
- *   (100 * int(1 + sqrt(N) / 1500), made odd), workspace (device) >= OT_FOCUS_WS + n_px * n_px doubles.
+ *   (100 * int(1 + sqrt(N) / 1500), made odd), workspace (device) >= OT_FOCUS_WS + n_px * n_px doubles.  After the
+ *   call workspace[0..3] hold the extent x_min, x_max, y_min, y_max of the hits at the last z sample and, for the
+ *   image methods, workspace + OT_FOCUS_WS holds the n_px x n_px image of that sample (row = y pixel).
  * ot_focus_moments: sums[16] (device) for __focus_rms_spot_direct_solution (raytracer.py:1420-1460), the mean
  *   position and the RMS cost curve: [0..4] = sum w, w pa_x, w pa_y, w sb_x, w sb_y; [5] = sum w^2 (dtx^2 + dty^2);
  *   [6] = sum w^2 (dtx dx + dty dy) for the bounds b0 < b1; [7] = sum w^2; [8..10] = sum w x0'^2, w x0' sbx', w sbx'^2

@@ -40,7 +40,10 @@ def test_focus_search_matches_reference(cname):
             if mi == 0:
                 assert err.max() < 1e-9, (method, err.max())
             else:
-                # a hit within rounding of a pixel edge may fall into the neighbour pixel at single samples
+                # a hit within rounding of a pixel edge may fall into the neighbour pixel at single samples.  The looseness
+                # comes from the two tracers' lines differing (1e-11), not from the kernels: on the device's own lines every
+                # one of these samples agrees with a longdouble host evaluation within the summation bound, with no sample
+                # ambiguous (test_gpu_focus_kernels.py::test_scene_curves_on_the_device_lines).
                 assert np.quantile(err, 0.97) < 1e-8 and err.max() < 0.05, (method, np.sort(err)[-5:])
             span = d["bounds"][1] - d["bounds"][0]
             xr, fr = float(f[f"{k}/x"]), float(f[f"{k}/fun"])
