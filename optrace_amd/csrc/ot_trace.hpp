@@ -120,17 +120,32 @@ OT_DEV void refraction_polarization(const V3& n, const V3& s, const V3& s_, doub
     double mm = dot3(m, m), mp = dot3(m, pol), sp = dot3(s, pol), np_ = dot3(n, pol);
     // n and s exactly parallel (a collimated beam along a face normal) while s' still differs from s by rounding:
     // the plane of incidence is undefined (m = 0, 1 / mm not finite).  The reference builds its basis from the
-    // rounding noise s' x s and gets A_ts^2 + A_tp^2 = |pol|^2 with ts = tp, i.e. the normal-incidence transmission
-    // and an unchanged pol -- which is the unchanged-direction branch.
-    if (!(mm > 0)) mask = false;
+    // rounding noise s' x s: it loses up to 2e-3 of the weight that way, or divides 0 by 0 where the noise cancels
+    // (tests/test_refraction_host.py).  The limit is the normal-incidence transmission (ts = tp) and an unchanged pol
+    // -- which is the unchanged-direction branch.
+    // Nearly parallel as well: mp and tp each carry an absolute rounding error of ~2^-53 against a magnitude of |m|, so
+    // below |m| ~ 2^-25 their squares over mm stop adding up to |pol_perp|^2 (on a tilted normal at |m| = 2^-48 the weight
+    // was off by 4 % and could exceed the incoming one).  There ts = tp to |m|^2 and pol' = pol to |m|: the split between
+    // the two amplitudes does not matter, their sum |pol|^2 - (s.pol)^2 does -- the float32 pol is unit only to 1e-7.
+    // 2^-54: at |m| = 2^-27 both forms are good to 2^-26 relative, below the float32 store.  m == 0 keeps 1/2 + 1/2, the
+    // reference's contract for an unchanged direction.  One comparison on the common path (it replaces mm > 0); the rest
+    // sits behind a wave-uniform branch that the waves of an ordinary bundle skip.
+    const bool near = !(mm >= 0x1p-54);  // m == 0 and NaN included
+    double half = 0.5;
+    if (__ballot(near) != 0ull) {
+        if (near) {
+            mask = false;
+            if (mm > 0) half = 0.5 * (dot3(pol, pol) - sp * sp);
+        }
+    }
     double inv = fast_rcp(mm);
     double tp = ns * sp - np_;   // A_tp |m|
     double ct = N - q * ns;      // s . s'
     A_ts2 = mp * mp * inv;
     A_tp2 = tp * tp * inv;
     if (!mask) {
-        A_ts2 = 0.5;
-        A_tp2 = 0.5;
+        A_ts2 = half;
+        A_tp2 = half;
     }
     if (mask) {
         V3 vec = {W * s.x - ct * n.x, W * s.y - ct * n.y, W * s.z - ct * n.z};
