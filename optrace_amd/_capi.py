@@ -202,6 +202,7 @@ SIGNATURES = {
 
 FOCUS_WS = 16  # OT_FOCUS_WS
 HIT_PIECES = 1024  # OT_HIT_PIECES
+DET_MAX = 8  # OT_DET_MAX in csrc/ot_detector.hpp: detectors per call of ot_detector_hits_multi / ot_detector_images
 ABI_VERSION = 9  # OT_ABI_VERSION
 ERR_UNSUPPORTED = -3  # OT_ERR_UNSUPPORTED
 OT_DEFER_INDEX, OT_DEFER_POL = 1, 2  # ot_scene_set_deferred_planes

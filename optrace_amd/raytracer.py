@@ -480,11 +480,6 @@ class Raytracer(Group):
             raise IndexError("Invalid source_index.")
         return int(self.rays.B_list[source_index]), int(self.rays.B_list[source_index + 1])
 
-    def _detector_label(self, detector_index: int) -> str:
-        det = self.detectors[detector_index]
-        title = f": {det.desc}" if det.desc else ""
-        return f"{Detector.abbr}{detector_index}{title} at z = {det.pos[2]:.5g} mm"
-
     def _warn_ill(self, ill_count: int, detector_index: int) -> None:
         if ill_count:
             warning(f"{ill_count} rays ({100*ill_count/self.rays.N:.3g}% of all rays) were ill-conditioned for "
@@ -492,10 +487,14 @@ class Raytracer(Group):
                     "Where and whether they intersect might be wrong.")
 
     def _detector_requests(self, specs: list, rays=None, no_rays: bool = False) -> list:
-        """Checks of `_hit_detector` (raytracer.py:897-920) and, per spec, everything the device calls need:
-        dicts with Ns, Ne (ray range), surf_desc, projection (name), crop (user extent or None), desc, centre.
+        """Checks of `_hit_detector` (raytracer.py:897-920) and, per spec, the `detector.DetectorRequest` the device calls
+        take.  specs: dicts with detector_index, source_index, extent, projection_method and optionally pos (the detector is
+        moved there first, as `iterative_render` does position by position, raytracer.py:1244), auto_extent (`_auto_extents`),
+        want_z, compact, weights_only; or requests made already, which come back as they are.
         `rays`: a `TailStorage` to take the rays from instead of `self.rays` (all its slots, no per-source ranges);
         `no_rays`: no storage yet (`_plan_renders` before the first trace): nothing about rays is checked or recorded."""
+        if specs and isinstance(specs[0], _detector.DetectorRequest):
+            return specs
         if not self.detectors:
             raise RuntimeError("Detector Missing")
         if rays is None and not no_rays:
@@ -503,16 +502,17 @@ class Raytracer(Group):
         ranges = []
         for sp in specs:  # all indices first: nothing is moved or launched for a bad request
             if no_rays:  # (a plan made before the rays exist: it ranges over the whole of whatever storage it is launched on)
-                ranges.append((0, 0))
+                ranges.append((0, None))
             else:
-                ranges.append(self._ray_range(sp.get("source_index")) if rays is None else (0, int(rays.N)))
+                Ns, Ne = self._ray_range(sp.get("source_index")) if rays is None else (0, int(rays.N))
+                ranges.append((Ns, Ne - Ns))
             if not 0 <= sp.get("detector_index", 0) < len(self.detectors):
                 raise IndexError("Invalid detector_index.")
         if rays is None and not no_rays:
             self._need_current()
 
         out = []
-        for sp, (Ns, Ne) in zip(specs, ranges):
+        for sp, (first, count) in zip(specs, ranges):
             k = sp.get("detector_index", 0)
             det = self.detectors[k]
             if sp.get("pos") is not None:
@@ -531,46 +531,40 @@ class Raytracer(Group):
             extent = sp.get("extent")
             if not (extent is None or isinstance(extent, (list, np.ndarray))):
                 raise ValueError(f"Invalid extent '{extent}'.")
-            crop = None if extent is None else np.asarray_chkfinite(np.array(extent, dtype=np.float64), dtype=np.float64)
-            out.append(dict(Ns=Ns, Ne=Ne, surf_desc=dsurf._desc(), projection=projection, crop=crop,
-                            desc=self._detector_label(k), centre=det.pos[:2].repeat(2),
-                            want_z=bool(sp.get("want_z", False))))
+            # An automatic extent crops like a user extent.  One of ALL the hits loses none by that; one taken from a sample of
+            # the rays or agreed with other ranks then treats the first chunk of an iterative render like the later ones, which
+            # are cropped to this very extent (`_extent0`, raytracer.py:1262) -- without the crop the margin `_fix_extent` adds
+            # around it (and the band a line-like image is widened to) would collect hits of the first chunk only
+            crop = sp.get("auto_extent")
+            if extent is not None:
+                crop = np.asarray_chkfinite(np.array(extent, dtype=np.float64), dtype=np.float64)
+            elif crop is not None:
+                crop = np.asarray(crop, dtype=np.float64)
+            title = f": {det.desc}" if det.desc else ""
+            out.append(_detector.DetectorRequest(
+                first, count, dsurf._desc(), projection, crop, k, sp.get("source_index"),
+                f"{Detector.abbr}{k}{title} at z = {det.pos[2]:.5g} mm", bool(sp.get("want_z", False)),
+                bool(sp.get("compact", False)), bool(sp.get("weights_only", False))))
         return out
 
-    def _hit_detectors(self, info: str, specs: list, _reqs: list = None) -> list:
+    def _hit_detectors(self, specs: list) -> list:
         """Device hit search for several (detector, position) pairs in one pass over the ray sections.
 
-        specs: dicts with detector_index, source_index, extent, projection_method and optionally pos (the detector is
-        moved there first, as `iterative_render` does position by position, raytracer.py:1244).
-        -> per spec (ph, hw, wl, extent_out, projection, ill_count, desc): device tensors of the selected ray range; ph
-        holds the x and y planes, the z plane as well with want_z
-        (dense: rays without a valid hit carry weight 0), the extent actually used, the projection name, the
-        ill-conditioned count and the image description at that position."""
-        reqs = self._detector_requests(specs) if _reqs is None else _reqs  # (`_reqs`: formed by the caller already)
-        groups: dict = {}  # ray range -> requests (one launch per range and at most 8 detectors)
-        for n, rq in enumerate(reqs):
+        specs: as for `_detector_requests`.  -> per spec a `detector.DetectorHits`: device tensors of the selected ray range
+        (xy: the x and y planes, the z plane as well with want_z; dense: rays without a valid hit carry weight 0), the extent
+        actually used, the projection name, the ill-conditioned count and the detector's description at that position."""
+        reqs = self._detector_requests(specs)
+        out = [None] * len(reqs)
+        for part, rqs in _detector.batches(reqs):
+            Ns, count = rqs[0].first, rqs[0].count
             # rays outside a user extent are dropped (raytracer.py:1036-1040): the hit kernel gives them weight 0
-            groups.setdefault((rq["Ns"], rq["Ne"]), []).append(
-                (n, dict(surf_desc=rq["surf_desc"], want_extent=rq["crop"] is None,
-                         projection=_capi.PROJECTIONS[rq["projection"]], crop=rq["crop"], want_z=rq["want_z"],
-                         compact=bool(specs[n].get("compact", False)),
-                         weights_only=bool(specs[n].get("weights_only", False)))))
-
-        out = [None] * len(specs)
-        for (Ns, Ne), part_all in groups.items():
-            for b in range(0, len(part_all), 8):
-                part = part_all[b:b + 8]
-                res = _detector.detector_hits_multi(self.rays, Ns, Ne - Ns, [r for _, r in part])
-                for (n, _), one in zip(part, res):
-                    ph, hw, ext4, ill_count = one[:4]
-                    rq = reqs[n]
-                    extent_out = rq["crop"]
-                    if extent_out is None:
-                        extent_out = ext4.copy() if np.all(np.isfinite(ext4)) else rq["centre"]
-                    wl = self.rays._dev["wl"][Ns:Ne]
-                    if len(one) > 4:  # compact list: its own wavelengths, and the fill counts ride along with them
-                        wl = one[4]
-                    out[n] = (ph, hw, wl, extent_out, rq["projection"], ill_count, rq["desc"])
+            res = _detector.detector_hits_multi(self.rays, Ns, count, rqs)
+            for n, rq, hl in zip(part, rqs, res):
+                extent_out = rq.crop
+                if extent_out is None:
+                    extent_out = hl.extent if np.all(np.isfinite(hl.extent)) else rq.centre
+                wl = self.rays._dev["wl"][Ns:Ns + count] if hl.wl is None else hl.wl
+                out[n] = _detector.DetectorHits(hl.ph, hl.hw, wl, extent_out, rq.projection, hl.ill_count, rq.label, hl.fill)
         return out
 
     def _render_detectors(self, specs: list, limits: list, into: list = None, rays=None, weight_scale: float = 1.0,
@@ -593,64 +587,44 @@ class Raytracer(Group):
 
     def _plan_renders(self, specs: list, limits: list, into: list = None, rays=None, whole_storage: bool = False) -> dict:
         """Everything `_render_detectors` does on the host before the launch: checks, the detectors moved to their positions,
-        one `RenderImage` per spec with its fixed extent and pixel grid, the histograms (one zero-filled allocation for all
-        images that have none yet) and the request records of `ot_detector_images`.  `whole_storage`: the requests range over
+        one `RenderImage` per spec on its fixed grid, the histograms (one zero-filled allocation for all images that have
+        none yet) and with them the image grid of every request.  `whole_storage`: the requests range over
         whatever storage `_launch_renders` is given (no source_index) -- `iterative_render` plans once, before its first trace
-        where the extents are known, and launches the plan chunk after chunk."""
+        where the extents are known, and launches the plan chunk after chunk.  -> dict(images, requests)"""
         reqs = self._detector_requests(specs, rays, no_rays=whole_storage)
-        images, calls, shapes = [], {}, []
+        images = []
         dev = require_device()
-        for n, (sp, rq, limit) in enumerate(zip(specs, reqs, limits)):
-            label = rq["desc"]
-            if sp.get("source_index") is not None:
-                label = f"Rays from RS{sp['source_index']} at {label}"
-            # the image extent: the user extent, or an automatic one (`_auto_extents`); the hits are cropped to it either
-            # way.  An automatic extent of ALL the hits loses none by that; one taken from a sample of the rays or agreed with
-            # other ranks then treats the first chunk of an iterative render like the later ones, which are cropped to this
-            # very extent (`_extent0`, raytracer.py:1262) -- without the crop the margin `_fix_extent` adds around it (and the
-            # band a line-like image is widened to) would collect hits of the first chunk only
-            if rq["crop"] is None:
-                rq["crop"] = np.asarray(sp["auto_extent"], dtype=np.float64)
-            img = RenderImage(extent=rq["crop"], projection=rq["projection"], long_desc=label)
-            img._limit = limit
-            img._fix_extent()
-            Nx, Ny = img._pixel_counts()
+        for n, (rq, limit) in enumerate(zip(reqs, limits)):  # (the image extent is the crop: the user or the automatic extent)
+            img, rq.Nx, rq.Ny = RenderImage.on_grid(rq.crop, rq.projection, rq.image_label, limit)
+            rq.extent = img.extent
             tgt = None if into is None else into[n]
-            if tgt is not None and tuple(tgt.shape) != (Ny, Nx, 4):
-                raise ValueError("histogram to accumulate into has the wrong shape")
+            if tgt is not None:
+                if tuple(tgt.shape) != (rq.Ny, rq.Nx, 4):
+                    raise ValueError("histogram to accumulate into has the wrong shape")
+                rq.hist = tgt.view(-1)
             images.append(img)
-            shapes.append((Ny, Nx, tgt))
         # the new histograms: ONE zero-filled allocation, sliced (six images of an iterative render: one fill kernel)
-        sizes = [Ny * Nx * 4 if tgt is None else 0 for Ny, Nx, tgt in shapes]
+        sizes = [rq.Ny * rq.Nx * 4 if rq.hist is None else 0 for rq in reqs]
         pool = alloc_retry(lambda: torch.zeros(sum(sizes), dtype=torch.float64, device=dev)) if sum(sizes) else None
         off = 0
-        for n, (img, rq, (Ny, Nx, tgt)) in enumerate(zip(images, reqs, shapes)):
-            if tgt is not None:
-                hist = tgt.view(-1)
-            else:
-                hist = pool[off:off + sizes[n]]
-                off += sizes[n]
-            img._dev = hist.view(Ny, Nx, 4)
-            img._host = None
-            calls.setdefault(None if whole_storage else (rq["Ns"], rq["Ne"]), []).append(
-                (n, dict(surf_desc=rq["surf_desc"], projection=_capi.PROJECTIONS[rq["projection"]], crop=rq["crop"],
-                         extent=img.extent, Nx=Nx, Ny=Ny, hist=hist)))
-        return dict(images=images, calls=calls, detector_indices=[sp.get("detector_index", 0) for sp in specs])
+        for img, rq, size in zip(images, reqs, sizes):
+            if rq.hist is None:
+                rq.hist = pool[off:off + size]
+                off += size
+            img._attach(rq.hist, rq.Nx, rq.Ny)
+        return dict(images=images, requests=reqs)
 
     def _launch_renders(self, plan: dict, rays=None, weight_scale: float = 1.0) -> None:
         """`ot_detector_images` for a plan of `_plan_renders`, on `rays` (a `TailStorage`) or `self.rays`."""
         src_rays = self.rays if rays is None else rays
-        for key, part_all in plan["calls"].items():
-            Ns, Ne = (0, int(src_rays.N)) if key is None else key
-            if Ne <= Ns:  # (a render-only chunk none of whose rays survived)
+        for _, rqs in _detector.batches(plan["requests"]):
+            first, count = rqs[0].first, rqs[0].count if rqs[0].count is not None else int(src_rays.N)
+            if count <= 0:  # (a render-only chunk none of whose rays survived)
                 continue
-            for b in range(0, len(part_all), 8):
-                part = part_all[b:b + 8]
-                for _, r in part:
-                    r["weight_scale"] = weight_scale
-                ills = _detector.detector_images(src_rays, Ns, Ne - Ns, [r for _, r in part])
-                for (n, _), ill_count in zip(part, ills):
-                    self._warn_ill(ill_count, plan["detector_indices"][n])
+            for rq in rqs:
+                rq.weight_scale = weight_scale
+            for rq, ill_count in zip(rqs, _detector.detector_images(src_rays, first, count, rqs)):
+                self._warn_ill(ill_count, rq.detector_index)
 
     def _auto_extents(self, specs: list, agree=None, sample_rays: int = None, rays=None) -> list:
         """Automatic extents (raytracer.py:1042-1049) of the specs without a user extent, from an extent-only pass over
@@ -668,49 +642,39 @@ class Raytracer(Group):
         traced = None if rays is None else int(rays.traced)
         raw = np.empty((len(todo), 4), dtype=np.float64)
         raw[:] = [np.inf, -np.inf, np.inf, -np.inf]
-        groups: dict = {}
+        rest = []  # rows of `raw` that take the pass over all rays
         for m, n in enumerate(todo):
             rq = reqs[n]
-            count, proj = rq["Ne"] - rq["Ns"], _capi.PROJECTIONS[rq["projection"]]
-            if count < 1:
+            if rq.count < 1:
                 continue
-            n_gen = count if traced is None else traced
-            if sample_rays and n_gen >= 2 * sample_rays and _detector.auto_image_supported(rq["surf_desc"], proj):
-                raw[m] = _detector.detector_extent_sample(src_rays, rq["Ns"], count, rq["surf_desc"], proj,
+            n_gen = rq.count if traced is None else traced
+            if sample_rays and n_gen >= 2 * sample_rays and _capi.fused_ok(rq.surf, rq.proj_id):
+                raw[m] = _detector.detector_extent_sample(src_rays, rq.first, rq.count, rq.surf, rq.proj_id,
                                                           n_gen // sample_rays)
                 continue
-            groups.setdefault((rq["Ns"], rq["Ne"]), []).append(m)
-        for (Ns, Ne), ms in groups.items():
-            for b in range(0, len(ms), 8):
-                part = ms[b:b + 8]
-                res = _detector.detector_extents(src_rays, Ns, Ne - Ns, [
-                    dict(surf_desc=reqs[todo[m]]["surf_desc"], projection=_capi.PROJECTIONS[reqs[todo[m]]["projection"]])
-                    for m in part])
-                for m, (ext4, _) in zip(part, res):
-                    raw[m] = ext4
+            rest.append(m)
+        for part, rqs in _detector.batches([reqs[todo[m]] for m in rest]):
+            res = _detector.detector_extents(src_rays, rqs[0].first, rqs[0].count, rqs)
+            for i, (ext4, _) in zip(part, res):
+                raw[rest[i]] = ext4
         if agree is not None:
             raw = np.asarray(agree(raw), dtype=np.float64).reshape(len(todo), 4)
         out = [dict(sp) for sp in specs]
         for m, n in enumerate(todo):
-            out[n]["auto_extent"] = raw[m].copy() if np.all(np.isfinite(raw[m])) else reqs[n]["centre"]
+            out[n]["auto_extent"] = raw[m].copy() if np.all(np.isfinite(raw[m])) else reqs[n].centre
         return out
 
     def _hit_detector(self, info: str, detector_index: int = 0, source_index: int = None, extent=None,
                       projection_method: str = "Equidistant"):
         """One detector: (ph, hw, wl, extent_out, projection, ill_count), see `_hit_detectors`."""
-        return self._hit_detectors(info, [dict(detector_index=detector_index, source_index=source_index, extent=extent,
-                                               projection_method=projection_method, want_z=True)])[0][:6]
+        return self._hit_detectors([dict(detector_index=detector_index, source_index=source_index, extent=extent,
+                                         projection_method=projection_method, want_z=True)])[0][:6]
 
-    def _image_from_hits(self, hits: tuple, detector_index: int, source_index, limit, **kwargs) -> RenderImage:
-        """Bin one hit list of `_hit_detectors` into a RenderImage."""
-        xy, weights, wavelengths, extent_out, projection, ill_count, label = hits
-        if source_index is not None:
-            label = f"Rays from RS{source_index} at {label}"
-        image = RenderImage(extent=extent_out, projection=projection, long_desc=label)
-        if isinstance(wavelengths, tuple):  # compact hit list: (wavelengths, fill counts)
-            wavelengths, kwargs["_fill"] = wavelengths
-        image.render(xy, weights, wavelengths, limit=limit, **kwargs)
-        self._warn_ill(ill_count, detector_index)
+    def _image_from_hits(self, hits, rq, limit, **kwargs) -> RenderImage:
+        """Bin one hit list of `_hit_detectors` (`hits`, for the request `rq`) into a RenderImage."""
+        image = RenderImage(extent=hits.extent, projection=hits.projection, long_desc=rq.image_label)
+        image.render(hits.xy, hits.w, hits.wl, limit=limit, _fill=hits.fill, **kwargs)
+        self._warn_ill(hits.ill_count, rq.detector_index)
         return image
 
     def detector_image(self, detector_index: int = 0, source_index: int = None, extent=None,
@@ -720,35 +684,32 @@ class Raytracer(Group):
             warning("Using the limit parameter in combination with a user defined extent"
                     " will produce an incorrect detector image, as the rays outside the extent"
                     " are not included in the convolution calculation.")
-        spec = dict(detector_index=detector_index, source_index=source_index, extent=extent,
-                    projection_method=projection_method)
         # extent known: one pass, no hit positions in memory -- except for long bundles on a spherical detector whose
         # projection has a transcendental (`ot_detector_images` would send that request through the chain with a dense hit
         # list; the chain over a compact list of the hits inside the extent is faster, C3 1.55 -> 1.4 ms)
         projected = (0 <= detector_index < len(self.detectors) and self.rays.N >= self.COMPACT_HITS_FROM
                      and isinstance(self.detectors[detector_index].surface, SphericalSurface)
                      and projection_method in ("Equidistant", "Equal-Area", "Stereographic"))
-        if extent is not None and not kwargs.get("_unfused", False) and not projected:
-            return self._render_detectors([spec], [limit], **kwargs)[0]
+        # (long bundles: a hit list holds the valid hits only, gathered piece-wise -- a third of the bytes for C4)
+        rq = self._detector_requests([dict(
+            detector_index=detector_index, source_index=source_index, extent=extent, projection_method=projection_method,
+            compact=(extent is None or projected) and self.rays.N >= self.COMPACT_HITS_FROM)])[0]
+        unfused = kwargs.pop("_unfused", False)
+        if extent is not None and not unfused and not projected:
+            return self._render_detectors([rq], [limit], **kwargs)[0]
         # Automatic extent: hit list first, then the binning.  (Measured against an extent-only pass followed by the
         # fused kernels, `_auto_extents` + `_render_detectors`, profiles/r3/detector_full_size.txt: C4 5.7 against 5.8 ms,
         # C5 3.7 / 3.6, and slower where the fused entry point falls back to this chain anyway -- spherical detectors, C3
         # 3.0 against 1.9 ms -- or the image is point-like, C2 1.3 against 0.9 ms: the sections are read twice either
         # way.  The extent-only pass serves where hit lists would have to be kept or exchanged: the first chunk of
         # `iterative_render` and the sharded forms in distributed.py.)
-        unfused = kwargs.pop("_unfused", False)
         # Long bundles, detectors with a closed-form hit: the sections are read once, the hits are sorted on a provisional
         # tile grid while their extent is found (`_auto_image_one_pass`; None: not applicable, the chain below runs)
-        reqs = None
         if not unfused and self.rays.N >= self.AUTO_ONE_PASS_FROM:
-            reqs = self._detector_requests([spec])  # (formed once: the chain below uses them where the one-pass form declines)
-            img = self._auto_image_one_pass(spec, limit, _rq=reqs[0], **kwargs)
+            img = self._auto_image_one_pass(rq, limit, **kwargs)
             if img is not None:
                 return img
-        # (long bundles: the hit list holds the valid hits only, gathered piece-wise -- a third of the bytes for C4)
-        spec["compact"] = (extent is None or projected) and self.rays.N >= self.COMPACT_HITS_FROM
-        hits = self._hit_detectors("Detector Image", [spec], _reqs=reqs)[0]
-        return self._image_from_hits(hits, detector_index, source_index, limit, **kwargs)
+        return self._image_from_hits(self._hit_detectors([rq])[0], rq, limit, **kwargs)
 
     @staticmethod
     def _auto_grid(e0, limit, projection, margins):
@@ -762,10 +723,7 @@ class Raytracer(Group):
         MR, side = RenderImage.MAX_IMAGE_RATIO, RenderImage.MAX_IMAGE_SIDE
         if min(sx0, sy0) <= 0 or max(sx0, sy0) / min(sx0, sy0) > MR / 1.2:
             return None
-        probe = RenderImage(extent=np.array(e0, dtype=np.float64), projection=projection)
-        probe._limit = limit
-        probe._fix_extent()
-        sx, sy = probe.s
+        sx, sy = RenderImage.on_grid(np.array(e0, dtype=np.float64), projection, limit=limit)[0].s
         n_long = side * min(MR, 1 + 2 * int(1.2 * max(sx, sy) / min(sx, sy) / 2))
         Nx0, Ny0 = (n_long, side) if sx > sy else (side, n_long)
         tw, th = 60 * sx / Nx0, 60 * sy / Ny0
@@ -776,23 +734,21 @@ class Raytracer(Group):
                 return (e0[0] - margin * sx0, e0[2] - margin * sy0, tw, th, tx, ty), tw, th
         return None
 
-    def _auto_image_one_pass(self, spec: dict, limit, _rq: dict = None, **kwargs):
-        """Image with an automatic extent (raytracer.py:1042-1049, 1053-1098) in one pass over the ray sections
-        (`detector.AutoImage`, csrc/ot_detector_fused.hpp last section).  The extent E0 of the hits of a sample of the
+    def _auto_image_one_pass(self, rq, limit, **kwargs):
+        """Image with an automatic extent (raytracer.py:1042-1049, 1053-1098) of the request `rq` in one pass over the ray
+        sections (`detector.AutoImage`, csrc/ot_detector_fused.hpp last section).  The extent E0 of the hits of a sample of the
         rays lies inside the final extent E, so the pixels of E's image are at least as large as those of E0's own
         image; tiles of 60 such pixels therefore fit 64 x 64 windows of the final grid.  -> RenderImage, or None where
         this form does not apply (detector with a numeric hit search or a sphere projection, no hit in the sample,
         point- / line-like or very elongated sample extent, too many hits outside the provisional grid): the caller
         takes the hit-list chain."""
-        rq = self._detector_requests([spec])[0] if _rq is None else _rq
-        Ns, count = rq["Ns"], rq["Ne"] - rq["Ns"]
-        sd, proj = rq["surf_desc"], _capi.PROJECTIONS[rq["projection"]]
-        if count < 1 or not _detector.auto_image_supported(sd, proj):
+        Ns, count, sd, proj = rq.first, rq.count, rq.surf, rq.proj_id
+        if count < 1 or not _capi.fused_ok(sd, proj):
             return None
         e0 = _detector.detector_extent_sample(self.rays, Ns, count, sd, proj, self.AUTO_SAMPLE_STRIDE)
         if not np.all(np.isfinite(e0)):
             return None
-        plan = self._auto_grid(e0, limit, rq["projection"], self.AUTO_MARGINS)
+        plan = self._auto_grid(e0, limit, rq.projection, self.AUTO_MARGINS)
         if plan is None:
             return None
         grid, tw, th = plan
@@ -806,20 +762,13 @@ class Raytracer(Group):
         if auto.escaped > auto.escape_capacity or not np.all(np.isfinite(auto.extent)):
             auto.cancel()
             return None
-        label = rq["desc"]
-        if spec.get("source_index") is not None:
-            label = f"Rays from RS{spec['source_index']} at {label}"
-        img = RenderImage(extent=auto.extent.copy(), projection=rq["projection"], long_desc=label)
-        img._limit = limit
-        img._fix_extent()
-        Nx, Ny = img._pixel_counts()
+        img, Nx, Ny = RenderImage.on_grid(auto.extent.copy(), rq.projection, rq.image_label, limit)
         if tw * Nx / img.s[0] > 61 or th * Ny / img.s[1] > 61:  # a tile would not fit its window (ratio snapped further)
             auto.cancel()
             return None
         hist = alloc_retry(lambda: torch.zeros(Ny * Nx * 4, dtype=torch.float64, device=require_device()))
         auto.finish(img.extent, Nx, Ny, hist)
-        img._dev = hist.view(Ny, Nx, 4)
-        img._host = None
+        img._attach(hist, Nx, Ny)
         if limit is not None and not kwargs.get("_dont_filter", False):
             img._apply_rayleigh_filter()
         return img
@@ -830,15 +779,12 @@ class Raytracer(Group):
         # long bundles: a compact list of the valid hits' weights and wavelengths (no positions: 8 B per valid hit written
         # instead of 28 B per ray, and the two histogram passes read those alone)
         compact = self.rays.N >= self.COMPACT_HITS_FROM
-        spec_rq = dict(detector_index=detector_index, source_index=source_index, extent=extent,
-                       projection_method="Equidistant", want_z=not compact, compact=compact, weights_only=compact)
-        _, w, wl, _, _, ill_count = self._hit_detectors("Detector Spectrum", [spec_rq])[0][:6]
-        if isinstance(wl, tuple):
-            wl, kwargs["_fill"] = wl
-
+        hits = self._hit_detectors([dict(detector_index=detector_index, source_index=source_index, extent=extent,
+                                         projection_method="Equidistant", want_z=not compact, compact=compact,
+                                         weights_only=compact)])[0]
         prefix = "Spectrum at " if source_index is None else f"Spectrum of RS{source_index} at "
-        spec = LightSpectrum.render(wl, w, long_desc=prefix + self._detector_label(detector_index), **kwargs)
-        self._warn_ill(ill_count, detector_index)
+        spec = LightSpectrum.render(hits.wl, hits.w, _fill=hits.fill, long_desc=prefix + hits.label, **kwargs)
+        self._warn_ill(hits.ill_count, detector_index)
         return spec
 
     def spot_analysis(self, detector_index: int = 0, source_index: int = None, extent=None,
@@ -850,15 +796,13 @@ class Raytracer(Group):
         freq = _spot.check_arguments(n_radii, frequencies)
         require_device()  # (said before anything about the rays: without a device there are none)
         # (long bundles: the list of the valid hits only, as for the detector image)
-        spec = dict(detector_index=detector_index, source_index=source_index, extent=extent,
-                    projection_method=projection_method, compact=self.rays.N >= self.COMPACT_HITS_FROM)
-        xy, w, wl, extent_out, _, ill_count, label = self._hit_detectors("Spot Analysis", [spec])[0]
-        fill = wl[1] if isinstance(wl, tuple) else None  # compact hit list: (wavelengths, fill counts)
-        if source_index is not None:
-            label = f"Rays from RS{source_index} at {label}"
-        first, end = self._ray_range(source_index)
-        sa = _spot.analyse(xy, w, end - first, fill, extent_out, n_radii, freq, long_desc="Spot at " + label)
-        self._warn_ill(ill_count, detector_index)
+        rq = self._detector_requests([dict(detector_index=detector_index, source_index=source_index, extent=extent,
+                                           projection_method=projection_method,
+                                           compact=self.rays.N >= self.COMPACT_HITS_FROM)])[0]
+        hits = self._hit_detectors([rq])[0]
+        sa = _spot.analyse(hits.xy, hits.w, rq.count, hits.fill, hits.extent, n_radii, freq,
+                           long_desc="Spot at " + rq.image_label)
+        self._warn_ill(hits.ill_count, detector_index)
         return sa
 
     # ---- source side (raytracer.py:1281-1352) ---------------------------------------------------------------

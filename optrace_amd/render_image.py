@@ -119,9 +119,25 @@ class RenderImage(BaseClass):
         """Nx, Ny: the smaller side has 945 px, the ratio snaps to 1, 3 or 5 (render_image.py:383-387)."""
         Nrs = self.MAX_IMAGE_SIDE
         nf = lambda a: min(self.MAX_IMAGE_RATIO, 1 + 2 * int(a / 2))  # noqa: E731
-        Nx = Nrs if self.s[0] <= self.s[1] else Nrs * nf(self.s[0] / self.s[1])
-        Ny = Nrs if self.s[0] > self.s[1] else Nrs * nf(self.s[1] / self.s[0])
-        return Nx, Ny
+        sx, sy = self.s
+        return (Nrs, Nrs * nf(sy / sx)) if sx <= sy else (Nrs * nf(sx / sy), Nrs)
+
+    def _grid(self, limit) -> tuple[int, int]:
+        """Fix the grid for the resolution limit `limit`: the extent as `_fix_extent` widens it.  -> Nx, Ny"""
+        self._limit = limit
+        self._fix_extent()
+        return self._pixel_counts()
+
+    @classmethod
+    def on_grid(cls, extent, projection: str = None, long_desc: str = "", limit: float = None) -> tuple:
+        """An image of this extent, projection, label and limit on its fixed grid, no histogram yet.  -> (image, Nx, Ny)"""
+        img = cls(extent=extent, projection=projection, long_desc=long_desc)
+        return (img,) + img._grid(limit)
+
+    def _attach(self, hist: "torch.Tensor", Nx: int, Ny: int) -> None:
+        """`hist` (flat f64 device tensor of Ny * Nx * 4 entries) becomes the image."""
+        self._dev = hist.view(Ny, Nx, 4)
+        self._host = None
 
     def render(self, p=None, w=None, wl=None, limit: float = None, _dont_filter: bool = False,
                _keep_on_device: bool = False, _into: "torch.Tensor" = None, _fill: "torch.Tensor" = None) -> None:
@@ -132,9 +148,7 @@ class RenderImage(BaseClass):
         The image stays in HBM; `_data` copies it to the host when it is first read (`_keep_on_device` is accepted
         for older callers and has no effect).  `_fill`: the device lists are a compact hit list (`ot_detector_req.fill`).
         """
-        self._limit = limit
-        self._fix_extent()
-        Nx, Ny = self._pixel_counts()
+        Nx, Ny = self._grid(limit)
         lib = _capi.load_library()
         dev = require_device()
         if _into is not None:  # accumulate into an existing (Ny, Nx, 4) device histogram (chunked rendering)
@@ -162,8 +176,7 @@ class RenderImage(BaseClass):
             else:
                 _capi.check(lib.ot_render_accumulate(n, ptr(px), ptr(py), ptr(dw), ptr(dwl), ext, Nx, Ny,
                                                      ptr(hist), stream_ptr()))
-        self._dev = hist.view(Ny, Nx, 4)
-        self._host = None
+        self._attach(hist, Nx, Ny)
         if self._limit is not None and not _dont_filter:
             self._apply_rayleigh_filter()
 

@@ -116,10 +116,9 @@ def test_not_applicable_cases_take_the_chain():
         RT.add(ot.Detector(ot.SphericalSurface(r=7.5, R=-30), pos=[0, 0, 150]))
         RT.trace(300_000)
         with one_pass_from(1):
-            assert RT._auto_image_one_pass(dict(detector_index=1, source_index=None, extent=None,
-                                                projection_method="Equidistant"), None) is None
-            assert RT._auto_image_one_pass(dict(detector_index=2, source_index=None, extent=None,
-                                                projection_method="Equidistant"), None) is None
+            for k in (1, 2):
+                spec = dict(detector_index=k, source_index=None, extent=None, projection_method="Equidistant")
+                assert RT._auto_image_one_pass(RT._detector_requests([spec])[0], None) is None
             a, a1 = RT.detector_image(), RT.detector_image(detector_index=1)
         with one_pass_from(1 << 60):
             b, b1 = RT.detector_image(), RT.detector_image(detector_index=1)
@@ -145,19 +144,16 @@ def test_any_grid_gives_the_same_image(grid_kind):
     grid = {"coarse tiles": (e[0] - 0.1 * sx, e[2] - 0.1 * sy, sx / 4, sy / 3, 5, 5),
             "half covered": (e[0] + 0.45 * sx, e[2] - 0.1 * sy, sx / 16, sy / 16, 12, 20),
             "one tile": (e[0] - sx, e[2] - sy, 3 * sx, 3 * sy, 1, 1)}[grid_kind]
-    auto = _detector.AutoImage(RT.rays, rq["Ns"], rq["Ne"] - rq["Ns"], rq["surf_desc"], _capi.PROJECTIONS[None], grid)
+    auto = _detector.AutoImage(RT.rays, rq.first, rq.count, rq.surf, _capi.PROJECTIONS[None], grid)
     np.testing.assert_array_equal(auto.extent, np.asarray(e, dtype=np.float64))
     if grid_kind == "half covered":
         assert 0 < auto.escaped <= auto.escape_capacity
     else:
         assert auto.escaped == 0
-    img = ot.RenderImage(extent=auto.extent.copy())
-    img._limit = None
-    img._fix_extent()
-    Nx, Ny = img._pixel_counts()
+    img, Nx, Ny = ot.RenderImage.on_grid(auto.extent.copy())
     hist = torch.zeros(Ny * Nx * 4, dtype=torch.float64, device="cuda")
     auto.finish(img.extent, Nx, Ny, hist)
-    img._dev, img._host = hist.view(Ny, Nx, 4), None
+    img._attach(hist, Nx, Ny)
     same_image(img, chain)
 
 
@@ -165,7 +161,7 @@ def test_escape_list_overflow_is_reported_and_cancel_frees():
     RT = image_scene(N=2_000_000)
     rq = _rq(RT)
     grid = (100.0, 100.0, 1.0, 1.0, 2, 2)  # nowhere near the image: every hit escapes
-    auto = _detector.AutoImage(RT.rays, rq["Ns"], rq["Ne"] - rq["Ns"], rq["surf_desc"], _capi.PROJECTIONS[None], grid)
+    auto = _detector.AutoImage(RT.rays, rq.first, rq.count, rq.surf, _capi.PROJECTIONS[None], grid)
     assert auto.escaped > auto.escape_capacity >= 1 << 18
     assert np.all(np.isfinite(auto.extent))
     auto.cancel()
@@ -177,16 +173,16 @@ def test_escape_list_overflow_is_reported_and_cancel_frees():
 def test_argument_checks():
     RT = image_scene(N=5000)
     rq = _rq(RT)
-    n = rq["Ne"] - rq["Ns"]
+    n = rq.count
     for grid in [(0.0, 0.0, 0.0, 1.0, 4, 4), (0.0, 0.0, 1.0, 1.0, 0, 4), (np.nan, 0.0, 1.0, 1.0, 4, 4)]:
         with pytest.raises(_capi.BackendError):
-            _detector.AutoImage(RT.rays, rq["Ns"], n, rq["surf_desc"], _capi.PROJECTIONS[None], grid)
+            _detector.AutoImage(RT.rays, rq.first, n, rq.surf, _capi.PROJECTIONS[None], grid)
     with pytest.raises(_capi.BackendError):  # more tiles than a workgroup keeps counters for
-        _detector.AutoImage(RT.rays, rq["Ns"], n, rq["surf_desc"], _capi.PROJECTIONS[None], (0.0, 0.0, 1.0, 1.0, 64, 64))
+        _detector.AutoImage(RT.rays, rq.first, n, rq.surf, _capi.PROJECTIONS[None], (0.0, 0.0, 1.0, 1.0, 64, 64))
     with pytest.raises(_capi.BackendError):  # sphere projection
-        _detector.detector_extent_sample(RT.rays, rq["Ns"], n, rq["surf_desc"], _capi.PROJECTIONS["Equidistant"], 128)
+        _detector.detector_extent_sample(RT.rays, rq.first, n, rq.surf, _capi.PROJECTIONS["Equidistant"], 128)
     with pytest.raises(_capi.BackendError):
-        _detector.detector_extent_sample(RT.rays, rq["Ns"], n + 1, rq["surf_desc"], _capi.PROJECTIONS[None], 128)
-    e = _detector.detector_extent_sample(RT.rays, rq["Ns"], n, rq["surf_desc"], _capi.PROJECTIONS[None], 1)
+        _detector.detector_extent_sample(RT.rays, rq.first, n + 1, rq.surf, _capi.PROJECTIONS[None], 128)
+    e = _detector.detector_extent_sample(RT.rays, rq.first, n, rq.surf, _capi.PROJECTIONS[None], 1)
     with one_pass_from(1 << 60), ot.global_options.no_warnings():
         np.testing.assert_array_equal(e, RT.detector_image()._extent0)  # stride 1: every ray

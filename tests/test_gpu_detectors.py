@@ -197,13 +197,18 @@ def test_one_pass_form_served_every_closed_form_kind():
 
 
 # ---- batches, spectra, ray counts ---------------------------------------------------------------------------------
+def record(surf, proj, **kw):
+    """a request over ray ranges given with the call, without a crop: the hits' extent comes back"""
+    return _detector.DetectorRequest(0, None, surf, proj, None, 0, None, "", **kw)
+
+
 def request(RT, di, proj, **kw):
-    return dict(surf_desc=RT.detectors[di].surface._desc(), projection=_capi.PROJECTIONS[proj], want_extent=True, crop=None, **kw)
+    return record(RT.detectors[di].surface._desc(), proj, **kw)
 
 
 def compact_rows(res, count):
     """rows (x, y, w, wl) of a compact hit list, sorted"""
-    ph, hw, ext, ill, (wl, fill) = res
+    ph, hw, ext, ill, wl, fill = res
     plen = int(_capi.load_library().ot_hit_piece_len(int(count)))
     cap = _capi.HIT_PIECES * plen
     ph, hw, wl, fill = ph.cpu().numpy(), hw.cpu().numpy(), wl.cpu().numpy(), fill.cpu().numpy()
@@ -229,8 +234,8 @@ def test_batches_equal_single_requests(n):
     for kind, place, proj in BATCH[:n]:  # one detector object per request (a kind may stand at one place at a time)
         surf = scenes.detector_kinds(ot)[kind]
         surf.move_to(fx.record(f"objective/{kind}/{place}/{proj}")["pos"])
-        dets.append((surf._desc(), _capi.PROJECTIONS[proj]))
-    mk = lambda j, **kw: dict(surf_desc=dets[j][0], projection=dets[j][1], want_extent=True, crop=None, **kw)  # noqa: E731
+        dets.append((surf._desc(), proj))
+    mk = lambda j, **kw: record(*dets[j], **kw)  # noqa: E731
     single = [_detector.detector_hits_multi(RT.rays, 0, N, [mk(j, want_z=True)])[0] for j in range(n)]
     dense = _detector.detector_hits_multi(RT.rays, 0, N, [mk(j, want_z=True) for j in range(n)])
     compact = _detector.detector_hits_multi(RT.rays, 0, N, [mk(j, compact=True) for j in range(n)])

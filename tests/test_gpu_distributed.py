@@ -186,8 +186,8 @@ def _single_process_iter(world, extent):
                 plan = RT._chunk_plan(b - a, len(RT.tracing_surfaces) + 2, True)
                 RT.trace(plan[-1], _chunk=len(plan) - 1, _power_scale=(b - a) / N_RAYS)
                 for k, p in enumerate(pos):
-                    e = RT._hit_detectors("Detector Image", [dict(detector_index=0, extent=None, pos=p,
-                                                                  projection_method="Equidistant")])[0][3]
+                    e = RT._hit_detectors([dict(detector_index=0, extent=None, pos=p,
+                                                projection_method="Equidistant")])[0][3]
                     lo[k], hi[k] = np.minimum(lo[k], e[[0, 2]]), np.maximum(hi[k], e[[1, 3]])
             agreed = np.stack([lo[:, 0], hi[:, 0], lo[:, 1], hi[:, 1]], axis=1)
         total, msgs, exts = None, 0, None

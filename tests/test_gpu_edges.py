@@ -186,8 +186,8 @@ def test_batched_detector_hits_equal_single_calls():
                  for k, z in enumerate(zs)]
         specs += [dict(detector_index=0, pos=[0, 0, 36.], projection_method=pm, extent=None)
                   for pm in ("Equidistant", "Orthographic")]
-        single = [RT._hit_detectors("t", [sp])[0] for sp in specs]
-        batch = RT._hit_detectors("t", specs)
+        single = [RT._hit_detectors([sp])[0] for sp in specs]
+        batch = RT._hit_detectors(specs)
         assert len(batch) == len(specs)
         hits = 0
         for a, b in zip(single, batch):

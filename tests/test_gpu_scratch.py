@@ -24,14 +24,11 @@ def stats(lib):
 def auto_image(RT, N):
     """(AutoImage, RenderImage to finish into, histogram) for detector 0 of RT."""
     rq = RT._detector_requests([dict(detector_index=0, source_index=None, extent=None, projection_method="Equidistant")])[0]
-    sd, proj = rq["surf_desc"], _capi.PROJECTIONS[rq["projection"]]
+    sd, proj = rq.surf, rq.proj_id
     e0 = _detector.detector_extent_sample(RT.rays, 0, N, sd, proj, 16)
-    grid, tw, th = RT._auto_grid(e0, None, rq["projection"], RT.AUTO_MARGINS)
+    grid, tw, th = RT._auto_grid(e0, None, rq.projection, RT.AUTO_MARGINS)
     auto = _detector.AutoImage(RT.rays, 0, N, sd, proj, grid)
-    img = ot.RenderImage(extent=auto.extent.copy(), projection=None)
-    img._limit = None
-    img._fix_extent()
-    Nx, Ny = img._pixel_counts()
+    img, Nx, Ny = ot.RenderImage.on_grid(auto.extent.copy())
     return auto, img, torch.zeros(Ny * Nx * 4, dtype=torch.float64, device="cuda"), (Nx, Ny)
 
 

@@ -49,8 +49,8 @@ def run(name, RT, N):
     if os.environ.get("AB_KNOWN"):
         e = [float(v) for v in out["one pass image"]._extent0]
         t = timeit(lambda: RT.detector_image(extent=e, _keep_on_device=True))
-        h = RT._hit_detectors("", [dict(detector_index=0, source_index=None, extent=None, compact=True)])[0]
-        print(f"{name:4s} extent given: {t[0]:6.2f} ms (median {t[1]:6.2f});  valid hits {int(h[2][1].sum().item()):,d} of {N:,d} rays", flush=True)
+        h = RT._hit_detectors([dict(detector_index=0, source_index=None, extent=None, compact=True)])[0]
+        print(f"{name:4s} extent given: {t[0]:6.2f} ms (median {t[1]:6.2f});  valid hits {int(h.fill.sum().item()):,d} of {N:,d} rays", flush=True)
     if "chain" not in out:
         print(f"{name:4s} N={N:11,d}  one pass {out['one pass'][0]:6.2f} ms (median {out['one pass'][1]:6.2f})  applied={all(applied) and bool(applied)}", flush=True)
         return

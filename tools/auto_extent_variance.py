@@ -22,10 +22,11 @@ def run(name, RT, N, reps=8):
         if os.environ.get("SPLIT"):
             spec = dict(detector_index=0, source_index=None, extent=None, projection_method="Equidistant",
                         compact=RT.rays.N >= RT.COMPACT_HITS_FROM)
-            hits = RT._hit_detectors("Detector Image", [spec])[0]
+            rq = RT._detector_requests([spec])[0]
+            hits = RT._hit_detectors([rq])[0]
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            RT._image_from_hits(hits, 0, None, None)
+            RT._image_from_hits(hits, rq, None)
             torch.cuda.synchronize()
             ts.append(1e3 * (t1 - t0)); ts.append(1e3 * (time.perf_counter() - t1))
             continue

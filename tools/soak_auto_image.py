@@ -47,7 +47,7 @@ for case in range(cases):
             ot.Raytracer.AUTO_SAMPLE_STRIDE, ot.Raytracer.AUTO_MARGINS = stride, margins
             ot.Raytracer.AUTO_ONE_PASS_FROM = 1
             spec = dict(detector_index=0, source_index=None, extent=None, projection_method=kw["projection_method"])
-            one = RT._auto_image_one_pass(spec, limit, _dont_filter=True)
+            one = RT._auto_image_one_pass(RT._detector_requests([spec])[0], limit, _dont_filter=True)
             ot.Raytracer.AUTO_ONE_PASS_FROM = 1 << 60
             chain = RT.detector_image(_dont_filter=True, **kw)
         finally:
