@@ -1,8 +1,24 @@
 // Host plumbing shared by the translation units of the C-ABI (ot_api.hip and ot_*_api.hip, one per stage): error reporting,
 // launch shapes, the scratch pool's front door, surface compilation and the source ranges.  Functions are declared here and
 // defined once, in the unit named beside them.  All of them are internal to the library: hidden visibility, so that the
-// dynamic symbol table holds the C-ABI and the trace launchers as before.
+// dynamic symbol table holds the C-ABI and the kernels' host stubs.
 #pragma once
+#include <stdint.h>
+
+// ---- ray chunks -----------------------------------------------------------------------------------------------------
+// Kernels with one ray per lane address their ray with 32-bit byte offsets from base pointers the host advances: a launch
+// covers at most 2^28 rays.  fn(base, n) is called for consecutive pieces of [first, first + count), n <= OT_RAY_CHUNK.
+// (Plain C++ ahead of the HIP includes: tests/cpp/ray_chunks_test.cpp compiles it with OT_HOST_CHUNKS_ONLY and no HIP.)
+#define OT_RAY_CHUNK ((int64_t)1 << 28)
+template <class F>
+static inline void for_ray_chunks(int64_t first, int64_t count, F&& fn) {
+    for (int64_t base = first; base < first + count; base += OT_RAY_CHUNK) {
+        const int64_t left = first + count - base;
+        fn(base, (uint32_t)(left < OT_RAY_CHUNK ? left : OT_RAY_CHUNK));
+    }
+}
+
+#ifndef OT_HOST_CHUNKS_ONLY
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -93,3 +109,4 @@ OT_INTERNAL size_t build_cdf_guide(const double* F, size_t n, double x0, CdfGuid
 
 // The inverse cumulative spectra of the three sRGB primaries, 3 x (OT_PRIM_M + 1) nodes (SourceDev::prim_inv).
 OT_INTERNAL const std::vector<double>& srgb_primary_inverse_tables();
+#endif  // OT_HOST_CHUNKS_ONLY

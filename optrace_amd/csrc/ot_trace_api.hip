@@ -1,5 +1,6 @@
-// C-ABI, trace stage: ray generation, the launchers of the trace kernel's variants (ot_trace_kernel.hpp, instantiated in
-// ot_trace_f*.hip / ot_trace_t*.hip), the counter reduction and the render-only tail storage.
+// C-ABI, trace stage: ray generation, the launches of the trace kernel's three forms (ot_trace_kernel.hpp, instantiated in
+// ot_trace_f*.hip / ot_trace_t*.hip / ot_trace_p*.hip), the counter reduction, the index and polarisation fills and the
+// render-only tail storage.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -68,6 +69,14 @@ static int check_rays(const ot_rays* r, bool need_pol) {
     return OT_OK;
 }
 
+// the storage of a scene's trace has one section per step and one before the first (`who`: the entry point, for the message)
+static int check_sections(const char* who, const ot_scene* sc, const ot_rays* rays) {
+    if (rays->nt != sc->h.nt)
+        return fail(OT_ERR_INVALID, std::string(who) + ": ray storage has " + std::to_string(rays->nt) +
+                                        " sections, the scene needs " + std::to_string(sc->h.nt));
+    return OT_OK;
+}
+
 extern "C" int ot_rays_generate(const ot_sources* src, const ot_source_range* ranges, int32_t n_ranges, uint64_t seed,
                                 int32_t no_pol, const ot_rays* rays, void* stream) {
     if (!src) return fail(OT_ERR_INVALID, "ot_rays_generate: null sources");
@@ -116,107 +125,111 @@ static TraceVariant trace_variant(const ot_scene* sc, const ot_sources* src, con
     return v;
 }
 
-// msgs: device counters the launch ADDS to, or nullptr: the counters of this launch alone go to the scene's pinned
-// host buffer (created on first use)
-// tail: render-only launch (trace_tail_kernel) of n_tail rays -- `rays` is not used then
-static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const RangeArgs* rg, const ot_rays* rays,
-                        const double* hurb_normals, uint64_t seed, int64_t* msgs, void* stream, const TailOut* tail = nullptr,
-                        int64_t n_tail = 0) {
-    ot_scene* sc = const_cast<ot_scene*>(sc_c);
-    if (!sc) return fail(OT_ERR_INVALID, "ot_trace: null argument");
-    bool pol = !sc->h.no_pol;
-    ot_rays tail_rays = {};
-    if (tail) {
-        tail_rays.N = n_tail;
-        rays = &tail_rays;
-    } else {
-        if (int rc = check_rays(rays, pol)) return rc;
-        if (rays->nt != sc->h.nt) return fail(OT_ERR_INVALID, "ray storage has " + std::to_string(rays->nt) +
-                                                                 " sections, the scene needs " + std::to_string(sc->h.nt));
-    }
+// ---- one launch path for the three forms ----------------------------------------------------------------------------------
+typedef void (*TraceLauncher)(const TraceLaunch&);
+#define OT_FORM_ROW(FORM)                                                                                              \
+    {launch_trace_unit<FORM, 0>, launch_trace_unit<FORM, 1>, launch_trace_unit<FORM, 2>, launch_trace_unit<FORM, 3>,    \
+     launch_trace_unit<FORM, 4>, launch_trace_unit<FORM, 5>}
+static const TraceLauncher k_trace_launchers[OT_N_FORMS][OT_N_FEATS] = {OT_FORM_ROW(OT_FORM_STORE), OT_FORM_ROW(OT_FORM_TAIL),
+                                                                        OT_FORM_ROW(OT_FORM_POL)};
+
+// What every launch of a trace has in common; the caller adds the storage (part or tail).  src / rg: null for rays handed in.
+static TraceLaunch make_launch(const ot_scene* sc, const ot_sources* src, const RangeArgs* rg, const TraceVariant& v,
+                               uint64_t seed, hipStream_t st) {
+    static const RangeArgs no_ranges = {};
+    TraceLaunch L = {};
+    L.lds = v.lds;
+    L.st = st;
+    L.sc = sc->d;
+    L.sd = src ? src->d : nullptr;
+    L.rg = rg ? rg : &no_ranges;
+    L.seed = seed;
+    L.slots = sc->cnt_slots;
+    L.pol = !sc->h.no_pol;
+    L.gen = src != nullptr;
+    L.spec = v.spec;
+    return L;
+}
+
+// launches the rays [base, base + n) of the bundle (one piece of for_ray_chunks)
+static void launch_chunk(int form, int feat, TraceLaunch& L, int64_t base, uint32_t n) {
+    L.base = base;
+    L.count = n;
+    L.grid = grid_for(n);
+    k_trace_launchers[form][feat](L);
+}
+
+static TailOut tail_out(const ot_rays* tail, uint32_t* fill) {
+    TailOut T;
+    T.p = tail->p;
+    T.w = tail->w;
+    T.wl = tail->wl;
+    T.fill = fill;
+    T.cap = tail->N;
+    return T;
+}
+
+static size_t msgs_bytes(const ot_scene* sc) { return sizeof(unsigned long long) * (size_t)(OT_N_INFOS * sc->h.nt + 1); }
+
+// the scene's pinned host buffer for the counters of one launch (created on first use)
+static int pinned_counters(ot_scene* sc) {
+    if (sc->pin_msgs) return OT_OK;
+    HIP_TRY(hipHostMalloc((void**)&sc->pin_msgs, msgs_bytes(sc), hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(sc->pin_msgs, 0, msgs_bytes(sc));
+    return OT_OK;
+}
+
+// The launches of one trace of n_rays rays -- each(base, n) launches a chunk --, timed if the scene asks for it, and the
+// counter reduction.  msgs: device counters the trace ADDS to, or nullptr: the counters of this trace alone go to the
+// scene's pinned host buffer.
+template <class F>
+static int trace_chunks(ot_scene* sc, int64_t n_rays, int64_t* msgs, hipStream_t st, F&& each) {
     const int n_cnt = OT_N_INFOS * sc->h.nt + 1;
-    if (!msgs && !sc->pin_msgs) {
-        HIP_TRY(hipHostMalloc((void**)&sc->pin_msgs, sizeof(unsigned long long) * (size_t)n_cnt,
-                              hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(sc->pin_msgs, 0, sizeof(unsigned long long) * (size_t)n_cnt);
-    }
-    if (rays->N == 0) {
-        if (!msgs) std::memset(sc->pin_msgs, 0, sizeof(unsigned long long) * (size_t)n_cnt);
-        return OT_OK;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    RangeArgs none;
-    none.n = 0;
-    none.ext = nullptr;
-    const RangeArgs& r = rg ? *rg : none;
-    const SourceDev* sd = src ? src->d : nullptr;
     unsigned long long* m = (unsigned long long*)msgs;
     if (!msgs) HIP_TRY(hipHostGetDevicePointer((void**)&m, sc->pin_msgs, 0));
-    const TraceVariant v = trace_variant(sc, src, hurb_normals);
-    if (v.error) return fail(OT_ERR_UNSUPPORTED, v.error);
-    const int feat = v.feat, spec = v.spec;
-    const size_t lds = v.lds;
-    unsigned int* slots = sc->cnt_slots;
-    if (!tail) sc->index_spec = spec;  // what ot_rays_fill_index has to repeat
     if (sc->timing) HIP_TRY(hipEventRecord(sc->ev0, st));
-    // lanes address their ray with 32-bit byte offsets: launches of at most 2^28 rays, base pointers advanced
-    const int64_t chunk = 1ll << 28;
-    for (int64_t base = 0; base < rays->N; base += chunk) {
-        TraceLaunch L;
-        L.count = (uint32_t)std::min<int64_t>(chunk, rays->N - base);
-        L.grid = grid_for(L.count);
-        L.lds = lds;
-        L.st = st;
-        L.sc = sc->d;
-        L.part = *rays;
-        if (!tail) {
-            L.part.p += base; L.part.s += base; L.part.w += base; L.part.n += base; L.part.wl += base;
-            if (L.part.pol) L.part.pol += base;
-            // deferred planes: a null base, the kernel skips the plane (ot_trace.hpp::store_section_next).  Rays handed in
-            // cannot be repeated and carry their polarisation in section 0 of the plane: ot_trace always stores it.
-            if (sc->deferred & OT_DEFER_INDEX) L.part.n = nullptr;
-            if ((sc->deferred & OT_DEFER_POL) && src) L.part.pol = nullptr;
-        }
-        L.sd = sd;
-        L.rg = &r;
-        L.hurb_normals = hurb_normals;
-        L.seed = seed;
-        L.slots = slots;
-        L.base = base;
-        L.pol = pol;
-        L.gen = src != nullptr;
-        L.spec = spec;
-        if (tail) {  // the render-only form of the same feature level
-            switch (feat) {
-                case OT_FEAT(OT_HIT_CLOSED, 0): launch_trace_tail_feat<OT_FEAT(OT_HIT_CLOSED, 0)>(L, *tail); break;
-                case OT_FEAT(OT_HIT_CLOSED, 1): launch_trace_tail_feat<OT_FEAT(OT_HIT_CLOSED, 1)>(L, *tail); break;
-                case OT_FEAT(OT_HIT_ILLINOIS, 0): launch_trace_tail_feat<OT_FEAT(OT_HIT_ILLINOIS, 0)>(L, *tail); break;
-                case OT_FEAT(OT_HIT_ILLINOIS, 1): launch_trace_tail_feat<OT_FEAT(OT_HIT_ILLINOIS, 1)>(L, *tail); break;
-                case OT_FEAT(OT_HIT_SPLINE, 0): launch_trace_tail_feat<OT_FEAT(OT_HIT_SPLINE, 0)>(L, *tail); break;
-                default: launch_trace_tail_feat<OT_FEAT(OT_HIT_SPLINE, 1)>(L, *tail); break;
-            }
-            continue;
-        }
-        switch (feat) {
-            case OT_FEAT(OT_HIT_CLOSED, 0): launch_trace_feat<OT_FEAT(OT_HIT_CLOSED, 0)>(L); break;
-            case OT_FEAT(OT_HIT_CLOSED, 1): launch_trace_feat<OT_FEAT(OT_HIT_CLOSED, 1)>(L); break;
-            case OT_FEAT(OT_HIT_ILLINOIS, 0): launch_trace_feat<OT_FEAT(OT_HIT_ILLINOIS, 0)>(L); break;
-            case OT_FEAT(OT_HIT_ILLINOIS, 1): launch_trace_feat<OT_FEAT(OT_HIT_ILLINOIS, 1)>(L); break;
-            case OT_FEAT(OT_HIT_SPLINE, 0): launch_trace_feat<OT_FEAT(OT_HIT_SPLINE, 0)>(L); break;
-            default: launch_trace_feat<OT_FEAT(OT_HIT_SPLINE, 1)>(L); break;
-        }
-    }
+    for_ray_chunks(0, n_rays, each);
     HIP_TRY(hipGetLastError());
     if (sc->timing) {
         HIP_TRY(hipEventRecord(sc->ev1, st));
         sc->ev_valid = true;
     }
     if (msgs)
-        hipLaunchKernelGGL(reduce_counters_kernel<true>, dim3(n_cnt), dim3(256), 0, st, slots, n_cnt, m);
+        hipLaunchKernelGGL(reduce_counters_kernel<true>, dim3(n_cnt), dim3(256), 0, st, sc->cnt_slots, n_cnt, m);
     else
-        hipLaunchKernelGGL(reduce_counters_kernel<false>, dim3(n_cnt), dim3(256), 0, st, slots, n_cnt, m);
+        hipLaunchKernelGGL(reduce_counters_kernel<false>, dim3(n_cnt), dim3(256), 0, st, sc->cnt_slots, n_cnt, m);
     HIP_TRY(hipGetLastError());
     return OT_OK;
+}
+
+// A stored trace: rays handed in (src and rg null) or generated on the device.
+static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const RangeArgs* rg, const ot_rays* rays,
+                        const double* hurb_normals, uint64_t seed, int64_t* msgs, void* stream) {
+    ot_scene* sc = const_cast<ot_scene*>(sc_c);
+    if (!sc) return fail(OT_ERR_INVALID, "ot_trace: null argument");
+    if (int rc = check_rays(rays, !sc->h.no_pol)) return rc;
+    if (int rc = check_sections("ot_trace", sc, rays)) return rc;
+    if (!msgs)
+        if (int rc = pinned_counters(sc)) return rc;
+    if (rays->N == 0) {
+        if (!msgs) std::memset(sc->pin_msgs, 0, msgs_bytes(sc));
+        return OT_OK;
+    }
+    const TraceVariant v = trace_variant(sc, src, hurb_normals);
+    if (v.error) return fail(OT_ERR_UNSUPPORTED, v.error);
+    sc->index_spec = v.spec;  // what ot_rays_fill_index has to repeat
+    TraceLaunch L = make_launch(sc, src, rg, v, seed, (hipStream_t)stream);
+    L.hurb_normals = hurb_normals;
+    return trace_chunks(sc, rays->N, msgs, L.st, [&](int64_t base, uint32_t n) {
+        L.part = *rays;
+        L.part.p += base; L.part.s += base; L.part.w += base; L.part.n += base; L.part.wl += base;
+        if (L.part.pol) L.part.pol += base;
+        // deferred planes: a null base, the kernel skips the plane (ot_trace.hpp::store_section_next).  Rays handed in
+        // cannot be repeated and carry their polarisation in section 0 of the plane: ot_trace always stores it.
+        if (sc->deferred & OT_DEFER_INDEX) L.part.n = nullptr;
+        if ((sc->deferred & OT_DEFER_POL) && src) L.part.pol = nullptr;
+        launch_chunk(OT_FORM_STORE, v.feat, L, base, n);
+    });
 }
 
 extern "C" int ot_trace(const ot_scene* scene, const ot_rays* rays, const double* hurb_normals, uint64_t seed,
@@ -244,7 +257,7 @@ extern "C" int ot_generate_and_trace_host(const ot_scene* scene, const ot_source
     if (int rc = make_ranges(ranges, n_ranges, src, rays->N, &rg)) return rc;
     if (int rc = launch_trace(scene, src, rg, rays, nullptr, seed, nullptr, stream)) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    std::memcpy(msgs_host, scene->pin_msgs, sizeof(int64_t) * (size_t)(OT_N_INFOS * scene->h.nt + 1));
+    std::memcpy(msgs_host, scene->pin_msgs, msgs_bytes(scene));
     return OT_OK;
 }
 
@@ -252,7 +265,7 @@ extern "C" int ot_generate_and_trace_host(const ot_scene* scene, const ot_source
 // alive or not, hit or not: section 0 carries the ambient medium, a refracting step (kind <= OT_STEP_IDEAL) the medium behind
 // it, every other step the index before it -- a function of (scene, section, wavelength) alone.  This kernel walks the same
 // steps with the same device functions the trace kernel of variant SPEC uses (medium_n<TAB>; SPEC 2: the rows of the
-// per-line table and the same comparison that finds a ray's line), so the plane is bit for bit what that trace stores when
+// per-line table and ray_line to find a ray's line), so the plane is bit for bit what that trace stores when
 // the scene's index store is on.  One ray per lane, 32-bit lane offsets from a wave-uniform plane base that advances by one
 // plane per section; streaming stores (the plane is written once and not read here).
 template <int SPEC>
@@ -267,11 +280,7 @@ __global__ __launch_bounds__(256) void fill_index_kernel(const SceneDev* __restr
     const auto pool = as_const(sc.pool);
     const float wl = wlp[local];
     const double* ltab = sc.line_tab;
-    int lj = 0;
-    if (SPEC == 2) {
-        for (int j = 1; j < sc.n_lines; j++)
-            if ((float)ltab[j] == wl) lj = j;
-    }
+    const int lj = ray_line<SPEC>(sc, ltab, wl);
     const double* lrow = ltab + OT_MAX_LINES + lj;  // row 0 of this lane's column (trace_ray)
     double n_cur = (SPEC == 2) ? lrow[(3 * sc.n_steps) * OT_MAX_LINES] : medium_n<TAB>(media[sc.n0], pool, wl);
     __builtin_nontemporal_store(n_cur, &plane[local]);
@@ -287,18 +296,14 @@ __global__ __launch_bounds__(256) void fill_index_kernel(const SceneDev* __restr
 extern "C" int ot_rays_fill_index(const ot_scene* sc, const ot_rays* rays, int64_t first, int64_t count, void* stream) {
     if (!sc || !rays) return fail(OT_ERR_INVALID, "ot_rays_fill_index: null argument");
     if (rays->N < 0 || !rays->n || !rays->wl) return fail(OT_ERR_INVALID, "ot_rays_fill_index: the ray storage needs n and wl");
-    if (rays->nt != sc->h.nt || rays->nt != sc->h.n_steps + 1)
-        return fail(OT_ERR_INVALID, "ray storage has " + std::to_string(rays->nt) + " sections, the scene needs " +
-                                        std::to_string(sc->h.nt));
+    if (int rc = check_sections("ot_rays_fill_index", sc, rays)) return rc;
     if (first < 0 || count < 0 || first + count > rays->N) return fail(OT_ERR_INVALID, "ot_rays_fill_index: range outside the storage");
     if (int rc = require_device()) return rc;
     // the variant of the scene's last stored trace; none yet: formulas, as a trace of rays handed in would take
     int spec = sc->index_spec >= 0 ? sc->index_spec : (sc->needs_tables ? 1 : 0);
     if (spec == 2 && sc->h.n_lines < 1) spec = sc->needs_tables ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t chunk = 1ll << 28;  // 32-bit lane offsets, as the trace launches
-    for (int64_t base = first; base < first + count; base += chunk) {
-        const uint32_t n = (uint32_t)std::min<int64_t>(chunk, first + count - base);
+    for_ray_chunks(first, count, [&](int64_t base, uint32_t n) {
         const float* wl = rays->wl + base;
         double* plane = rays->n + base;
         if (spec == 2)
@@ -307,21 +312,19 @@ extern "C" int ot_rays_fill_index(const ot_scene* sc, const ot_rays* rays, int64
             hipLaunchKernelGGL(fill_index_kernel<1>, grid_for(n), dim3(256), 0, st, sc->d, wl, plane, rays->N, n);
         else
             hipLaunchKernelGGL(fill_index_kernel<0>, grid_for(n), dim3(256), 0, st, sc->d, wl, plane, rays->N, n);
-    }
+    });
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }
 
 // The polarisation planes of a storage whose trace left them unwritten (OT_DEFER_POL): the trace once more, storing only them
-// (ot_trace_kernel.hpp::trace_pol_kernel).  Chunks and base advances as in launch_trace.
+// (ot_trace_kernel.hpp::trace_pol_kernel).
 extern "C" int ot_rays_fill_pol(const ot_scene* sc, const ot_sources* src, const ot_source_range* ranges, int32_t n_ranges,
                                 uint64_t seed, const ot_rays* rays, int64_t first, int64_t count, void* stream) {
     if (!sc || !src || !ranges || !rays) return fail(OT_ERR_INVALID, "ot_rays_fill_pol: null argument");
     if (sc->h.no_pol) return fail(OT_ERR_INVALID, "ot_rays_fill_pol: the scene does not track polarisation");
     if (rays->N < 0 || !rays->pol) return fail(OT_ERR_INVALID, "ot_rays_fill_pol: the ray storage needs pol");
-    if (rays->nt != sc->h.nt || rays->nt != sc->h.n_steps + 1)
-        return fail(OT_ERR_INVALID, "ot_rays_fill_pol: ray storage has " + std::to_string(rays->nt) + " sections, the scene needs " +
-                                        std::to_string(sc->h.nt));
+    if (int rc = check_sections("ot_rays_fill_pol", sc, rays)) return rc;
     if (first < 0 || count < 0 || first > rays->N || count > rays->N - first)
         return fail(OT_ERR_INVALID, "ot_rays_fill_pol: range outside the storage");
     if (int rc = require_device()) return rc;
@@ -329,34 +332,13 @@ extern "C" int ot_rays_fill_pol(const ot_scene* sc, const ot_sources* src, const
     if (int rc = make_ranges(ranges, n_ranges, src, rays->N, &rg)) return rc;
     const TraceVariant v = trace_variant(sc, src, nullptr);
     if (v.error) return fail(OT_ERR_UNSUPPORTED, v.error);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t chunk = 1ll << 28;
-    for (int64_t base = first; base < first + count; base += chunk) {
-        TraceLaunch L = {};
-        L.count = (uint32_t)std::min<int64_t>(chunk, first + count - base);
-        L.grid = grid_for(L.count);
-        L.lds = v.lds;
-        L.st = st;
-        L.sc = sc->d;
-        L.part = {};  // the kernel reads N, nt and pol
-        L.part.N = rays->N;
-        L.part.nt = rays->nt;
+    TraceLaunch L = make_launch(sc, src, rg, v, seed, (hipStream_t)stream);
+    L.part.N = rays->N;  // the kernel reads N, nt and pol
+    L.part.nt = rays->nt;
+    for_ray_chunks(first, count, [&](int64_t base, uint32_t n) {
         L.part.pol = rays->pol + base;
-        L.sd = src->d;
-        L.rg = rg;
-        L.seed = seed;
-        L.base = base;
-        L.pol = L.gen = true;
-        L.spec = v.spec;
-        switch (v.feat) {
-            case OT_FEAT(OT_HIT_CLOSED, 0): launch_trace_pol_feat<OT_FEAT(OT_HIT_CLOSED, 0)>(L); break;
-            case OT_FEAT(OT_HIT_CLOSED, 1): launch_trace_pol_feat<OT_FEAT(OT_HIT_CLOSED, 1)>(L); break;
-            case OT_FEAT(OT_HIT_ILLINOIS, 0): launch_trace_pol_feat<OT_FEAT(OT_HIT_ILLINOIS, 0)>(L); break;
-            case OT_FEAT(OT_HIT_ILLINOIS, 1): launch_trace_pol_feat<OT_FEAT(OT_HIT_ILLINOIS, 1)>(L); break;
-            case OT_FEAT(OT_HIT_SPLINE, 0): launch_trace_pol_feat<OT_FEAT(OT_HIT_SPLINE, 0)>(L); break;
-            default: launch_trace_pol_feat<OT_FEAT(OT_HIT_SPLINE, 1)>(L); break;
-        }
-    }
+        launch_chunk(OT_FORM_POL, v.feat, L, base, n);
+    });
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }
@@ -387,7 +369,7 @@ __global__ __launch_bounds__(256) void tail_seal_kernel(TailOut T, long long* __
     const unsigned int piece = blockIdx.x;
     const int64_t N = T.cap;
     for (unsigned int q = T.fill[piece] + threadIdx.x; q < rows * 64u; q += 256) {
-        const int64_t slot = (((int64_t)(q >> 6) * OT_TAIL_PIECES + piece) << 6) + (q & 63u);
+        const int64_t slot = tail_slot(q, piece);
         for (int c = 0; c < 6; c++) T.p[slot + c * N] = 0.0;
         T.w[slot] = 0.f;
         T.w[N + slot] = 0.f;
@@ -424,18 +406,20 @@ extern "C" int ot_generate_and_trace_tail(const ot_scene* scene, const ot_source
     const RangeArgs* rg = nullptr;
     if (int rc = make_ranges(ranges, n_ranges, src, n_rays, &rg)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    TailOut T;
-    T.p = tail->p;
-    T.w = tail->w;
-    T.wl = tail->wl;
-    T.fill = fill;
-    T.cap = tail->N;
+    const TailOut T = tail_out(tail, fill);
     HIP_TRY(hipMemsetAsync(fill, 0, sizeof(uint32_t) * OT_TAIL_PIECES, st));
-    if (int rc = launch_trace(scene, src, rg, nullptr, nullptr, seed, nullptr, stream, &T, n_rays)) return rc;
+    ot_scene* sc = const_cast<ot_scene*>(scene);
+    if (int rc = pinned_counters(sc)) return rc;
+    const TraceVariant v = trace_variant(sc, src, nullptr);
+    if (v.error) return fail(OT_ERR_UNSUPPORTED, v.error);
+    TraceLaunch L = make_launch(sc, src, rg, v, seed, st);  // (index_spec stays: no stored trace)
+    L.tail = T;
+    if (int rc = trace_chunks(sc, n_rays, nullptr, st, [&](int64_t base, uint32_t n) { launch_chunk(OT_FORM_TAIL, v.feat, L, base, n); }))
+        return rc;
     hipLaunchKernelGGL(tail_seal_kernel, dim3(OT_TAIL_PIECES), dim3(256), 0, st, T, (long long*)result2);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    std::memcpy(msgs_host, scene->pin_msgs, sizeof(int64_t) * (size_t)(OT_N_INFOS * scene->h.nt + 1));
+    std::memcpy(msgs_host, scene->pin_msgs, msgs_bytes(scene));
     return OT_OK;
 }
 
@@ -462,8 +446,7 @@ __global__ __launch_bounds__(256) void tail_append_kernel(ot_rays R, int64_t fir
     if (rank == 0 && alive) q0 = atomicAdd(&T.fill[piece], n_alive);
     q0 = __shfl(q0, __ffsll((long long)m) - 1);
     if (alive) {
-        const unsigned int qs = q0 + rank;
-        const int64_t slot = (((int64_t)(qs >> 6) * OT_TAIL_PIECES + piece) << 6) + (qs & 63u);
+        const int64_t slot = tail_slot(q0 + rank, piece);
         const int64_t C = T.cap;
         double* px = T.p + slot;
 #pragma unroll
@@ -489,12 +472,7 @@ extern "C" int ot_tail_append(const ot_rays* rays, int64_t first, int64_t count,
         return fail(OT_ERR_INVALID, "ot_tail_append: tail storage smaller than ot_tail_capacity(rays_before + count + 64)");
     if (int rc = require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
-    TailOut T;
-    T.p = tail->p;
-    T.w = tail->w;
-    T.wl = tail->wl;
-    T.fill = fill;
-    T.cap = tail->N;
+    const TailOut T = tail_out(tail, fill);
     if (count) hipLaunchKernelGGL(tail_append_kernel, grid_for(count), dim3(256), 0, st, *rays, first, count, T, waves_before, weight_scale);
     hipLaunchKernelGGL(tail_seal_kernel, dim3(OT_TAIL_PIECES), dim3(256), 0, st, T, (long long*)result2);
     HIP_TRY(hipGetLastError());

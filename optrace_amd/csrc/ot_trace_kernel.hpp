@@ -1,9 +1,12 @@
-// The tracing kernel and its launch plumbing, shared by the translation units that instantiate its variants.
+// The tracing kernel in its three forms and their launch plumbing, shared by the translation units that instantiate them.
 //
-// One translation unit per feature level (ot_trace_f<level>.hip) instantiates the 10 variants of that level
-// (polarisation x generation x spectrum handling); ot_trace_api.hip only calls launch_trace_feat<level>().  The render-only
-// form and the polarisation replay have units of their own (ot_trace_t<level>.hip, ot_trace_p<level>.hip).  The split is a
-// build-time matter (the variants compile in parallel, one level rebuilds alone) and changes nothing in the kernels.
+// The forms -- storing (trace_kernel), render-only (trace_tail_kernel), polarisation replay (trace_pol_kernel) -- are one frame
+// around trace_ray: the LDS layout, the start of a generated ray, the spectral-line lookup, the patch buffer and the counter
+// flush are the helpers below, so a form spells out only what it loads, what it stores and what it reports.  One translation
+// unit per form and feature level (ot_trace_f<level>.hip: the 10 storing variants, polarisation x generation x spectrum
+// handling; ot_trace_t<level>.hip: 6 render-only; ot_trace_p<level>.hip: 3 replays) defines launch_trace_unit<form, level>
+// through OT_DEFINE_TRACE_UNIT; ot_trace_api.hip calls them through a table.  The split is a build-time matter (the units
+// compile in parallel, one rebuilds alone) and changes nothing in the kernels.
 #pragma once
 #include "ot_trace.hpp"
 
@@ -160,6 +163,66 @@ OT_DEV bool generate_lane(const RangeArgs& rg, const SourceDev* __restrict__ sou
     return have;
 }
 
+// ---- the frame of the three kernel forms ----------------------------------------------------------------------------------
+// Dynamic LDS of a trace workgroup: [discrete-spectrum table (SPEC == 2)] [event counters + timeout flag] [spline patches]
+struct TraceLds {
+    double* ltab;       // (3 * n_steps + 2) rows of OT_MAX_LINES, staged from sc.line_tab
+    unsigned int* cnt;  // (OT_N_INFOS x nt) counters + 1 flag
+    int n_tab, n_cnt;
+};
+
+// zeroes the counters, stages the line table; ends with the workgroup's barrier
+template <int SPEC, class SC>
+OT_DEV TraceLds trace_lds_init(double* lds, SC& sc) {
+    TraceLds f;
+    f.n_tab = (SPEC == 2) ? (3 * sc.n_steps + 2) * OT_MAX_LINES : 0;
+    f.ltab = lds;
+    f.cnt = (unsigned int*)(lds + f.n_tab);
+    f.n_cnt = OT_N_INFOS * sc.nt + 1;
+    for (int k = threadIdx.x; k < f.n_cnt; k += blockDim.x) f.cnt[k] = 0u;
+    if (SPEC == 2)
+        for (int k = threadIdx.x; k < f.n_tab; k += blockDim.x) f.ltab[k] = sc.line_tab[k];
+    __syncthreads();
+    return f;
+}
+
+OT_DEV void start_ray(RayState& r, const NewRay& nr) {
+    r.p = nr.p;
+    r.s = nr.s;
+    r.w = nr.w;
+    r.wl = nr.wl;
+    r.polx = (float)nr.polx;
+    r.poly = (float)nr.poly;
+    r.polz = (float)nr.polz;
+}
+
+// discrete spectra: which line a ray of wavelength wl carries (row 0 of the line table holds the wavelengths).  The trace
+// kernels look it up in LDS, fill_index_kernel in the scene's table.
+template <int SPEC, class SC>
+OT_DEV int ray_line(SC& sc, const double* ltab, float wl) {
+    int lj = 0;
+    if (SPEC == 2) {
+        for (int j = 1; j < sc.n_lines; j++)
+            if ((float)ltab[j] == wl) lj = j;
+    }
+    return lj;
+}
+
+// spline level: 25 doubles per lane behind the counters for the spline patch cache.  (TraceLds goes by value here and in
+// flush_counters: by reference the SGPR spills of two storing kernels moved, profiles/trace_frame/parent_vs_branch.txt.)
+template <int FEAT>
+OT_DEV double* patch_base(double* lds, TraceLds f) {
+    return (FEAT / 2 >= OT_HIT_SPLINE) ? lds + f.n_tab + (f.n_cnt + 2) / 2 : nullptr;
+}
+
+// the workgroup's counters go to its slot table (blockIdx % slots), once every wave is through
+OT_DEV void flush_counters(TraceLds f, unsigned int* slots) {
+    __syncthreads();
+    unsigned int* slot = slots + (size_t)(blockIdx.x % OT_CNT_SLOTS) * f.n_cnt;
+    for (int k = threadIdx.x; k < f.n_cnt; k += blockDim.x)
+        if (f.cnt[k]) atomicAdd(&slot[k], f.cnt[k]);
+}
+
 // Raytracer.trace: optional on-the-fly generation, then all steps.  One ray per lane, 256-thread workgroups
 // (4 wave64); template switches select a kernel that only contains what the scene needs:
 //   POL  polarisation tracked          GEN  rays generated in registers (no section-0 round trip)
@@ -179,16 +242,9 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ke
                                                     const double* __restrict__ hurb_normals, uint64_t seed,
                                                     unsigned int* __restrict__ slots, int64_t ray_base,
                                                     uint32_t count) {
-    extern __shared__ double lds[];  // [discrete-spectrum table (SPEC == 2)] [event counters + timeout flag]
+    extern __shared__ double lds[];  // (TraceLds)
     auto& sc = *as_const(scp);
-    const int n_tab = (SPEC == 2) ? (3 * sc.n_steps + 2) * OT_MAX_LINES : 0;
-    double* ltab = lds;
-    unsigned int* cnt = (unsigned int*)(lds + n_tab);  // (OT_N_INFOS x nt) counters + 1 flag
-    const int n_cnt = OT_N_INFOS * sc.nt + 1;
-    for (int k = threadIdx.x; k < n_cnt; k += blockDim.x) cnt[k] = 0u;
-    if (SPEC == 2)
-        for (int k = threadIdx.x; k < n_tab; k += blockDim.x) ltab[k] = sc.line_tab[k];
-    __syncthreads();
+    const TraceLds f = trace_lds_init<SPEC>(lds, sc);
 
     const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t ray = ray_base + (int64_t)local;
@@ -199,13 +255,7 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ke
             NewRay nr;
             have = generate_lane<(SPEC != 2)>(rg, sources, ray, seed, !POL, nr);  // no image sources with SPEC 2 (launch_trace)
             if (have) {
-                r.p = nr.p;
-                r.s = nr.s;
-                r.w = nr.w;
-                r.wl = nr.wl;
-                r.polx = (float)nr.polx;
-                r.poly = (float)nr.poly;
-                r.polz = (float)nr.polz;
+                start_ray(r, nr);
                 __builtin_nontemporal_store(r.wl, &R.wl[local]);  // written once, streamed (see OT_STORE_HINT)
             }
         } else {
@@ -228,22 +278,14 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ke
     }
     // RaySource.create_rays raises if any generated direction has s_z <= 0 (ray_source.py:353).  Reported as
     // counter (HURB_NEG_DIR, section 0), a cell no tracing event can touch; the host turns it into that error.
-    if (GEN) count_event(cnt, sc.nt, OT_INFO_HURB_NEG_DIR, 0, have && !(r.s.z > 0));
+    if (GEN) count_event(f.cnt, sc.nt, OT_INFO_HURB_NEG_DIR, 0, have && !(r.s.z > 0));
     if (have) {
-        int lj = 0;  // discrete spectra: which line this ray carries
-        if (SPEC == 2) {
-            for (int j = 1; j < sc.n_lines; j++)
-                if ((float)ltab[j] == r.wl) lj = j;
-        }
-        // spline level: 25 doubles per lane behind the counters for the spline patch cache
-        double* patch = (FEAT / 2 >= OT_HIT_SPLINE) ? lds + n_tab + (n_cnt + 2) / 2 : nullptr;
-        bool ok = trace_ray<POL, SPEC, FEAT>(sc, R, local, (uint64_t)ray, r, hurb_normals, seed, cnt, ltab, lj, patch);
-        if (!ok) cnt[n_cnt - 1] = 1u;  // numeric hit search timed out (surface.py:403)
+        const int lj = ray_line<SPEC>(sc, f.ltab, r.wl);
+        bool ok = trace_ray<POL, SPEC, FEAT>(sc, R, local, (uint64_t)ray, r, hurb_normals, seed, f.cnt, f.ltab, lj,
+                                             patch_base<FEAT>(lds, f));
+        if (!ok) f.cnt[f.n_cnt - 1] = 1u;  // numeric hit search timed out (surface.py:403)
     }
-    __syncthreads();
-    unsigned int* slot = slots + (size_t)(blockIdx.x % OT_CNT_SLOTS) * n_cnt;
-    for (int k = threadIdx.x; k < n_cnt; k += blockDim.x)
-        if (cnt[k]) atomicAdd(&slot[k], cnt[k]);
+    flush_counters(f, slots);
 }
 
 // ---- render-only tracing: the living rays' LAST SECTION instead of every section -------------------------------------
@@ -268,20 +310,19 @@ struct TailOut {
     int64_t cap;         // plane stride = 65536 * rows
 };
 
+// slot q of piece `piece` in the interleaved storage.  (The wave allocation around it stays written out in trace_tail_kernel
+// and tail_append_kernel: every shared form tried moved the register allocation of the tail kernels, same file.)
+OT_DEV int64_t tail_slot(unsigned int q, unsigned int piece) {
+    return (((int64_t)(q >> 6) * OT_TAIL_PIECES + piece) << 6) + (q & 63u);
+}
+
 template <bool POL, int SPEC, int FEAT>
 __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_tail_kernel(
     const SceneDev* __restrict__ scp, TailOut T, const SourceDev* __restrict__ sources, RangeArgs rg, uint64_t seed,
     unsigned int* __restrict__ slots, int64_t ray_base, uint32_t count) {
-    extern __shared__ double lds[];  // as in trace_kernel
+    extern __shared__ double lds[];  // (TraceLds)
     auto& sc = *as_const(scp);
-    const int n_tab = (SPEC == 2) ? (3 * sc.n_steps + 2) * OT_MAX_LINES : 0;
-    double* ltab = lds;
-    unsigned int* cnt = (unsigned int*)(lds + n_tab);
-    const int n_cnt = OT_N_INFOS * sc.nt + 1;
-    for (int k = threadIdx.x; k < n_cnt; k += blockDim.x) cnt[k] = 0u;
-    if (SPEC == 2)
-        for (int k = threadIdx.x; k < n_tab; k += blockDim.x) ltab[k] = sc.line_tab[k];
-    __syncthreads();
+    const TraceLds f = trace_lds_init<SPEC>(lds, sc);
 
     const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t ray = ray_base + (int64_t)local;
@@ -295,29 +336,15 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ta
     if (have) {
         NewRay nr;
         have = generate_lane<(SPEC != 2)>(rg, sources, ray, seed, !POL, nr);
-        if (have) {
-            r.p = nr.p;
-            r.s = nr.s;
-            r.w = nr.w;
-            r.wl = nr.wl;
-            r.polx = (float)nr.polx;
-            r.poly = (float)nr.poly;
-            r.polz = (float)nr.polz;
-        }
+        if (have) start_ray(r, nr);
     }
-    count_event(cnt, sc.nt, OT_INFO_HURB_NEG_DIR, 0, have && !(r.s.z > 0));
+    count_event(f.cnt, sc.nt, OT_INFO_HURB_NEG_DIR, 0, have && !(r.s.z > 0));
     if (have) {
-        int lj = 0;
-        if (SPEC == 2) {
-            for (int j = 1; j < sc.n_lines; j++)
-                if ((float)ltab[j] == r.wl) lj = j;
-        }
+        const int lj = ray_line<SPEC>(sc, f.ltab, r.wl);
         const ot_rays none = {};
-        // spline level: 25 doubles per lane behind the counters for the spline patch cache (as in trace_kernel)
-        double* patch = (FEAT / 2 >= OT_HIT_SPLINE) ? lds + n_tab + (n_cnt + 2) / 2 : nullptr;
-        bool ok = trace_ray<POL, SPEC, FEAT, OT_STORE_NONE>(sc, none, local, (uint64_t)ray, r, (const double*)nullptr, seed, cnt, ltab, lj,
-                                                   patch, &tail);
-        if (!ok) cnt[n_cnt - 1] = 1u;
+        bool ok = trace_ray<POL, SPEC, FEAT, OT_STORE_NONE>(sc, none, local, (uint64_t)ray, r, (const double*)nullptr, seed, f.cnt, f.ltab,
+                                                            lj, patch_base<FEAT>(lds, f), &tail);
+        if (!ok) f.cnt[f.n_cnt - 1] = 1u;
     }
     // the living rays of this wave, compacted
     const bool alive = have && tail.w > 0.f;
@@ -331,8 +358,7 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ta
         if (rank == 0 && alive) q0 = atomicAdd(&T.fill[piece], n_alive);  // (the first living lane)
         q0 = __shfl(q0, __ffsll((long long)m) - 1);
         if (alive) {
-            const unsigned int q = q0 + rank;
-            const int64_t slot = (((int64_t)(q >> 6) * OT_TAIL_PIECES + piece) << 6) + (q & 63u);
+            const int64_t slot = tail_slot(q0 + rank, piece);
             const int64_t N = T.cap;
             double* px = T.p + slot;  // element (ray, section, component) at ray + N * (section + 2 * component)
             px[0] = tail.p.x;
@@ -346,10 +372,7 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ta
             T.wl[slot] = r.wl;
         }
     }
-    __syncthreads();
-    unsigned int* slot_tab = slots + (size_t)(blockIdx.x % OT_CNT_SLOTS) * n_cnt;
-    for (int k = threadIdx.x; k < n_cnt; k += blockDim.x)
-        if (cnt[k]) atomicAdd(&slot_tab[k], cnt[k]);
+    flush_counters(f, slots);
 }
 
 // ---- the polarisation planes, replayed (ot_rays_fill_pol) -------------------------------------------------------------------
@@ -363,16 +386,9 @@ template <int SPEC, int FEAT>
 __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, true)) void trace_pol_kernel(
     const SceneDev* __restrict__ scp, ot_rays R, const SourceDev* __restrict__ sources, RangeArgs rg, uint64_t seed,
     int64_t ray_base, uint32_t count) {
-    extern __shared__ double lds[];  // as in trace_kernel
+    extern __shared__ double lds[];  // (TraceLds)
     auto& sc = *as_const(scp);
-    const int n_tab = (SPEC == 2) ? (3 * sc.n_steps + 2) * OT_MAX_LINES : 0;
-    double* ltab = lds;
-    unsigned int* cnt = (unsigned int*)(lds + n_tab);
-    const int n_cnt = OT_N_INFOS * sc.nt + 1;
-    for (int k = threadIdx.x; k < n_cnt; k += blockDim.x) cnt[k] = 0u;
-    if (SPEC == 2)
-        for (int k = threadIdx.x; k < n_tab; k += blockDim.x) ltab[k] = sc.line_tab[k];
-    __syncthreads();
+    const TraceLds f = trace_lds_init<SPEC>(lds, sc);
 
     const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t ray = ray_base + (int64_t)local;
@@ -380,20 +396,10 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, true)) void trace_p
     NewRay nr;
     if (!generate_lane<(SPEC != 2)>(rg, sources, ray, seed, false, nr)) return;
     RayState r;
-    r.p = nr.p;
-    r.s = nr.s;
-    r.w = nr.w;
-    r.wl = nr.wl;
-    r.polx = (float)nr.polx;
-    r.poly = (float)nr.poly;
-    r.polz = (float)nr.polz;
-    int lj = 0;
-    if (SPEC == 2) {
-        for (int j = 1; j < sc.n_lines; j++)
-            if ((float)ltab[j] == r.wl) lj = j;
-    }
-    double* patch = (FEAT / 2 >= OT_HIT_SPLINE) ? lds + n_tab + (n_cnt + 2) / 2 : nullptr;
-    trace_ray<true, SPEC, FEAT, OT_STORE_POL>(sc, R, local, (uint64_t)ray, r, (const double*)nullptr, seed, cnt, ltab, lj, patch);
+    start_ray(r, nr);
+    const int lj = ray_line<SPEC>(sc, f.ltab, r.wl);
+    trace_ray<true, SPEC, FEAT, OT_STORE_POL>(sc, R, local, (uint64_t)ray, r, (const double*)nullptr, seed, f.cnt, f.ltab, lj,
+                                              patch_base<FEAT>(lds, f));
 }
 
 // Feature levels of the kernel variants.  Bit 0 ("full"): HURB, and at hit level 0 ideal lenses and filters as well (the
@@ -405,13 +411,18 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, true)) void trace_p
 #define OT_FEAT_HIT(feat) ((feat) / 2)
 #define OT_FEAT_FULL(feat) (((feat)&1) != 0)
 
+// the three forms of the kernel
+enum { OT_FORM_STORE = 0, OT_FORM_TAIL = 1, OT_FORM_POL = 2, OT_N_FORMS = 3 };
+#define OT_N_FEATS 6
+
 // everything a launch of one variant needs
 struct TraceLaunch {
     dim3 grid;
     size_t lds;
     hipStream_t st;
     const SceneDev* sc;
-    ot_rays part;
+    ot_rays part;  // OT_FORM_STORE: the storage, advanced to `base`; OT_FORM_POL: N, nt and pol of it
+    TailOut tail;  // OT_FORM_TAIL
     const SourceDev* sd;
     const RangeArgs* rg;
     const double* hurb_normals;
@@ -423,55 +434,41 @@ struct TraceLaunch {
     int spec;
 };
 
-// defined in ot_trace_f<FEAT>.hip through OT_DEFINE_TRACE_LAUNCHER
-template <int FEAT>
-void launch_trace_feat(const TraceLaunch& L);
-// render-only variants (generation on the device, no injected HURB normals): defined in ot_trace_t<FEAT>.hip
-template <int FEAT>
-void launch_trace_tail_feat(const TraceLaunch& L, const TailOut& T);
+// The launcher of one form and feature level: L.spec, L.pol and (storing form) L.gen pick the kernel.  Defined in
+// ot_trace_{f,t,p}<FEAT>.hip through OT_DEFINE_TRACE_UNIT, which is where the kernels are instantiated; internal to the
+// library.
+template <int FORM, int FEAT>
+__attribute__((visibility("hidden"))) void launch_trace_unit(const TraceLaunch& L);
 
-// polarisation replay (generation on the device, polarisation on): defined in ot_trace_p<FEAT>.hip
-template <int FEAT>
-void launch_trace_pol_feat(const TraceLaunch& L);
+template <int FORM, int FEAT, int SPEC, bool POL>
+static void launch_trace_kernel(const TraceLaunch& L) {
+    const dim3 block(256);
+    if constexpr (FORM == OT_FORM_TAIL)  // generation on the device, no injected HURB normals
+        hipLaunchKernelGGL((trace_tail_kernel<POL, SPEC, FEAT>), L.grid, block, L.lds, L.st, L.sc, L.tail, L.sd, *L.rg, L.seed,
+                           L.slots, L.base, L.count);
+    else if constexpr (FORM == OT_FORM_POL)  // generation on the device, polarisation on
+        hipLaunchKernelGGL((trace_pol_kernel<SPEC, FEAT>), L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg, L.seed, L.base,
+                           L.count);
+    else if (L.gen)
+        hipLaunchKernelGGL((trace_kernel<POL, true, SPEC, FEAT>), L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg,
+                           L.hurb_normals, L.seed, L.slots, L.base, L.count);
+    else if constexpr (SPEC != 2)  // (discrete spectra: generated rays only, see trace_variant)
+        hipLaunchKernelGGL((trace_kernel<POL, false, SPEC, FEAT>), L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg,
+                           L.hurb_normals, L.seed, L.slots, L.base, L.count);
+}
 
-#define OT_DEFINE_TRACE_POL_LAUNCHER(FEAT)                                                                              \
+template <int FORM, int FEAT, int SPEC>
+static void launch_trace_spec(const TraceLaunch& L) {
+    if (L.pol)  // (always set for the replay, whose kernel has no such switch)
+        launch_trace_kernel<FORM, FEAT, SPEC, true>(L);
+    else
+        launch_trace_kernel<FORM, FEAT, SPEC, false>(L);
+}
+
+#define OT_DEFINE_TRACE_UNIT(FORM, FEAT)                                                                                \
     template <>                                                                                                         \
-    void launch_trace_pol_feat<FEAT>(const TraceLaunch& L) {                                                            \
-        const dim3 block(256);                                                                                          \
-        auto go = [&](auto kern) {                                                                                      \
-            hipLaunchKernelGGL(kern, L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg, L.seed, L.base, L.count);   \
-        };                                                                                                              \
-        if (L.spec == 2) go(trace_pol_kernel<2, FEAT>);                                                                 \
-        else if (L.spec == 1) go(trace_pol_kernel<1, FEAT>);                                                            \
-        else go(trace_pol_kernel<0, FEAT>);                                                                             \
-    }
-
-#define OT_DEFINE_TRACE_TAIL_LAUNCHER(FEAT)                                                                             \
-    template <>                                                                                                         \
-    void launch_trace_tail_feat<FEAT>(const TraceLaunch& L, const TailOut& T) {                                         \
-        const dim3 block(256);                                                                                          \
-        auto go = [&](auto kern) {                                                                                      \
-            hipLaunchKernelGGL(kern, L.grid, block, L.lds, L.st, L.sc, T, L.sd, *L.rg, L.seed, L.slots, L.base, L.count); \
-        };                                                                                                              \
-        if (L.spec == 2) { if (L.pol) go(trace_tail_kernel<true, 2, FEAT>); else go(trace_tail_kernel<false, 2, FEAT>); } \
-        else if (L.spec == 1) { if (L.pol) go(trace_tail_kernel<true, 1, FEAT>); else go(trace_tail_kernel<false, 1, FEAT>); } \
-        else { if (L.pol) go(trace_tail_kernel<true, 0, FEAT>); else go(trace_tail_kernel<false, 0, FEAT>); }           \
-    }
-
-#define OT_DEFINE_TRACE_LAUNCHER(FEAT)                                                                                  \
-    template <>                                                                                                         \
-    void launch_trace_feat<FEAT>(const TraceLaunch& L) {                                                                \
-        const dim3 block(256);                                                                                          \
-        auto go = [&](auto kern) {                                                                                      \
-            hipLaunchKernelGGL(kern, L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg, L.hurb_normals, L.seed,     \
-                               L.slots, L.base, L.count);                                                               \
-        };                                                                                                              \
-        if (L.gen) {                                                                                                    \
-            if (L.spec == 2) { if (L.pol) go(trace_kernel<true, true, 2, FEAT>); else go(trace_kernel<false, true, 2, FEAT>); } \
-            else if (L.spec == 1) { if (L.pol) go(trace_kernel<true, true, 1, FEAT>); else go(trace_kernel<false, true, 1, FEAT>); } \
-            else { if (L.pol) go(trace_kernel<true, true, 0, FEAT>); else go(trace_kernel<false, true, 0, FEAT>); }     \
-        } else {                                                                                                        \
-            if (L.spec == 1) { if (L.pol) go(trace_kernel<true, false, 1, FEAT>); else go(trace_kernel<false, false, 1, FEAT>); } \
-            else { if (L.pol) go(trace_kernel<true, false, 0, FEAT>); else go(trace_kernel<false, false, 0, FEAT>); }   \
-        }                                                                                                               \
+    void launch_trace_unit<FORM, FEAT>(const TraceLaunch& L) {                                                          \
+        if (L.spec == 2) launch_trace_spec<FORM, FEAT, 2>(L);                                                           \
+        else if (L.spec == 1) launch_trace_spec<FORM, FEAT, 1>(L);                                                      \
+        else launch_trace_spec<FORM, FEAT, 0>(L);                                                                       \
     }

@@ -1,4 +1,4 @@
 // trace_pol_kernel variants (the polarisation planes replayed, ot_rays_fill_pol) of feature level OT_FEAT(OT_HIT_ILLINOIS, 0) (ot_trace_kernel.hpp)
 #include "ot_trace_kernel.hpp"
 
-OT_DEFINE_TRACE_POL_LAUNCHER(OT_FEAT(OT_HIT_ILLINOIS, 0))
+OT_DEFINE_TRACE_UNIT(OT_FORM_POL, OT_FEAT(OT_HIT_ILLINOIS, 0))

@@ -1,4 +1,4 @@
 // trace_tail_kernel variants (render-only chunks) of feature level OT_FEAT(OT_HIT_CLOSED, 0) (ot_trace_kernel.hpp)
 #include "ot_trace_kernel.hpp"
 
-OT_DEFINE_TRACE_TAIL_LAUNCHER(OT_FEAT(OT_HIT_CLOSED, 0))
+OT_DEFINE_TRACE_UNIT(OT_FORM_TAIL, OT_FEAT(OT_HIT_CLOSED, 0))

@@ -205,6 +205,14 @@ def freeform_scene(ot, ideal_lens=True, **rt_args):
     return RT
 
 
+def freeform_hurb_scene(ot, **rt_args):
+    """`freeform_scene` with HURB on and a slit aperture behind the tilted window: spline surfaces and HURB in one scene, the
+    highest feature level of the trace kernel (5)."""
+    RT = freeform_scene(ot, use_hurb=True, **rt_args)
+    RT.add(ot.Aperture(ot.SlitSurface(dim=[14, 14], dimi=[4, 3]), pos=[0, 0, 35]))
+    return RT
+
+
 # ---- function surfaces with a mask_func -------------------------------------------------------------------------------
 def _paraboloid(x, y):
     return 0.02 * (x ** 2 + 0.6 * y ** 2)

@@ -127,6 +127,8 @@ CASES = {
     "hurb_slit_lens": (lambda: scenes.hurb_slit_lens(ot, seed=8), N_SMALL),                     # Philox HURB deviates
     "double_gauss_aspheric": (lambda: scenes.double_gauss(ot, aspheric=True, seed=9), N_SMALL),
     "freeform": (lambda: scenes.freeform_scene(ot, seed=10), N_SMALL),                          # spline level
+    "asphere_hurb": (lambda: scenes.asphere_scene(ot, use_hurb=True, seed=13), N_SMALL),        # feature level 3
+    "freeform_hurb": (lambda: scenes.freeform_hurb_scene(ot, seed=14), N_SMALL),                # feature level 5
     "same_medium": (lambda: same_medium(seed=11), N_SMALL),
     "tir": (lambda: tir_scene(seed=12), N_SMALL),
 }

@@ -64,13 +64,18 @@ SCENES = {
 }
 
 
-@pytest.mark.parametrize("name", list(SCENES))
-@pytest.mark.parametrize("N", [1, 63, 65, 70_001, 1_300_000])
+# spline surfaces with HURB: feature level 5, which none of SCENES reaches (levels 0-4), at the sizes around one wave and at
+# the largest that stays quick
+EXTRA_SCENES = {"freeform_hurb": lambda **kw: scenes.freeform_hurb_scene(ot, **kw)}
+TAIL_CASES = [(N, name) for N in [1, 63, 65, 70_001, 1_300_000] for name in SCENES] + [(65, "freeform_hurb"), (70_001, "freeform_hurb")]
+
+
+@pytest.mark.parametrize("N,name", TAIL_CASES, ids=[f"{N}-{name}" for N, name in TAIL_CASES])
 def test_tail_records_are_the_stored_sections_bit_for_bit(name, N):
     """Same seed through `trace(N)` and `trace(N, _tail=...)`: the set of (p[nt-2], p[nt-1], w[nt-2], wl) over the rays alive
     in the last section is identical; every slot in use beyond them carries weight 0; counters equal."""
     with ot.global_options.no_warnings():
-        check_tail_records(SCENES[name](seed=17), N)
+        check_tail_records({**SCENES, **EXTRA_SCENES}[name](seed=17), N)
 
 
 @pytest.mark.parametrize("hurb", [False, True])
