@@ -728,6 +728,49 @@ int ot_spot_radial(int64_t n, const uint32_t* fill, const double* x, const doubl
 int ot_spot_otf(int64_t n, const uint32_t* fill, const double* x, const double* y, const float* w, const double* moments,
                 const double* freq, int32_t K, double* workspace, double* otf, void* stream);
 
+/* ---- wavefront analysis (Raytracer.wavefront_analysis; no counterpart in optrace) -------------------------------
+ * Optical path of the rays [first, first + count) of a storage to a reference sphere behind section `section`
+ * (0 .. nt - 2: from p[section] to p[section + 1]), and reductions of it.  A ray is used when w[section] > 0 and the section
+ * has a positive length L; its direction is s = (p[section + 1] - p[section]) / L.  Pointers are DEVICE unless said otherwise.
+ * Launches are ordered on `stream` and nothing is waited for.  Null arguments (wl apart), a ray range outside the storage, a
+ * section out of range, values that are not finite: OT_ERR_INVALID; limits exceeded: OT_ERR_UNSUPPORTED, both before a device
+ * is looked for; count = 0 / n = 0 returns OT_OK without a launch and leaves the outputs alone.
+ * ot_wavefront_focus: sums[OT_WF_FOCUS_M] = sum w | rays used | sum w q (3) | sum w s (3) | sum w (I - s s^T): xx xy xz yy yz
+ *   zz | sum w (I - s s^T) q (3), with q = p[section] - origin, origin[3] HOST.  The point closest to all ray lines solves
+ *   [sum w (I - s s^T)] (c - origin) = sum w (I - s s^T) q.  Reads p and w only.
+ * ot_wavefront_paths: per ray, with o = p[section] - focus (focus[3] HOST), b = s . o, D = b^2 - (o . o - radius^2) and
+ *   t = -b - sign(radius) sqrt(D): opl = sum_{j < section} n[j] |p[j + 1] - p[j]| + n[section] t, (u, v) = the x and y of
+ *   (o + t s) / |radius|, w_out = w[section].  Rays not used, and used ones with D < 0 -- counted in *missed -- get w_out = 0
+ *   and NaN elsewhere.  u, v, opl (f64) and w_out (f32) hold `count` entries each.  Reads p, w and n.
+ * ot_wavefront_moments: moments[OT_WF_M] over the entries with w > 0 (the others are not read into arithmetic) = sum w |
+ *   entries | sum w opl | sum w u | sum w v | sum w wl (0 where wl is NULL) | min opl | max opl | sum w (opl - mean)^2 |
+ *   max (du^2 + dv^2) about the means of the first pass: a second pass over the list | the root of that maximum, the pupil
+ *   radius the two calls below divide by.
+ * ot_wavefront_map: map[2 * n_grid * n_grid] (accumulated into: zero it first) += w | w (opl - mean) per cell
+ *   row * n_grid + column, column from x and row from y by min(floor((x + 1) / 2 * n_grid), n_grid - 1), (x, y) =
+ *   ((u, v) - mean) / pupil radius.  pupil_radius NaN: moments[10]; otherwise entries with x^2 + y^2 > 1 are left out.
+ *   1 <= n_grid <= OT_WF_MAX_GRID.  The one call whose sums depend on the order of arrival (f64 atomics).
+ * ot_wavefront_zernike: out[J (J + 1) / 2 + J] = the upper triangle of sum w Z Z^T row by row, then sum w Z (opl - mean), Z
+ *   the Noll-ordered orthonormal Zernike polynomials Z_1 .. Z_J at (x, y) as above, 1 <= J <= OT_WF_MAX_J.
+ * workspace >= OT_WF_WS doubles.  ot_wavefront_focus, _moments and _zernike add in an order fixed by the counts and J alone:
+ * the same call returns the same bits. */
+#define OT_WF_FOCUS_M 17
+#define OT_WF_M 11
+#define OT_WF_MAX_J 36
+#define OT_WF_MAX_GRID 1024
+#define OT_WF_BLOCKS 2048 /* most workgroups whose partial sums the workspace holds */
+#define OT_WF_WS (40 * OT_WF_BLOCKS)
+int ot_wavefront_focus(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const double* origin, double* workspace,
+                       double* sums, void* stream);
+int ot_wavefront_paths(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const double* focus, double radius,
+                       double* u, double* v, double* opl, float* w_out, int64_t* missed, void* stream);
+int ot_wavefront_moments(int64_t n, const double* u, const double* v, const double* opl, const float* w, const float* wl,
+                         double* workspace, double* moments, void* stream);
+int ot_wavefront_map(int64_t n, const double* u, const double* v, const double* opl, const float* w, const double* moments,
+                     double pupil_radius, int32_t n_grid, double* map, void* stream);
+int ot_wavefront_zernike(int64_t n, const double* u, const double* v, const double* opl, const float* w, const double* moments,
+                         double pupil_radius, int32_t J, double* workspace, double* out, void* stream);
+
 /* ---- samplers: optrace/tracer/random.py, Surface.random_positions, color.random_wavelengths_from_srgb ---------
  * The samplers of the ray generator (ot_rays_generate) as entry points of their own: sample i of a call is what the
  * generator draws for ray i of a launch with the same seed and the same ranges -- counter-based dither keyed by (seed, i),

@@ -18,6 +18,7 @@ from .geometry import (Surface, CircularSurface, RingSurface, RectangularSurface
 from .image import RGBImage, GrayscaleImage, ScalarImage
 from .render_image import RenderImage
 from .spot import SpotAnalysis
+from .wavefront import WavefrontAnalysis
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
 from .convolve import convolve

@@ -191,6 +191,11 @@ SIGNATURES = {
     "ot_spot_moments": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, vp]),
     "ot_spot_radial": (C.c_int, [i64, vp, vp, vp, vp, vp, i32, vp, vp]),
     "ot_spot_otf": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "ot_wavefront_focus": (C.c_int, [C.POINTER(Rays), i64, i64, i32, C.POINTER(C.c_double), vp, vp, vp]),
+    "ot_wavefront_paths": (C.c_int, [C.POINTER(Rays), i64, i64, i32, C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp, vp]),
+    "ot_wavefront_moments": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ot_wavefront_map": (C.c_int, [i64, vp, vp, vp, vp, vp, C.c_double, i32, vp, vp]),
+    "ot_wavefront_zernike": (C.c_int, [i64, vp, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp]),
     "ot_sample_stratified": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(SourceRange), i32, u64, i64, vp, vp, vp]),
     "ot_sample_positions": (C.c_int, [C.POINTER(Source), C.POINTER(SourceRange), i32, u64, i64, vp, vp]),
     "ot_sample_inverse": (C.c_int, [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i64, vp, i64, C.POINTER(SourceRange), i32,
@@ -209,6 +214,7 @@ OT_DEFER_INDEX, OT_DEFER_POL = 1, 2  # ot_scene_set_deferred_planes
 SAMPLE_INTERVAL, SAMPLE_RECTANGLE, SAMPLE_RING = range(3)  # OT_SAMPLE_*
 SAMPLE_DISCRETE, SAMPLE_CONTINUOUS = range(2)
 SPOT_M, SPOT_MAX_RADII, SPOT_MAX_FREQ = 8, 65536, 4096  # OT_SPOT_*
+WF_FOCUS_M, WF_M, WF_MAX_J, WF_MAX_GRID, WF_WS = 17, 11, 36, 1024, 40 * 2048  # OT_WF_*
 
 
 def spot_ws(K: int) -> int:

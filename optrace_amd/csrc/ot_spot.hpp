@@ -11,38 +11,13 @@
 // comes back to the host in between.
 // Defines kernels that are no templates: included by ot_spot_api.hip alone.
 #pragma once
+#include "ot_block_reduce.hpp"
 #include "ot_device.hpp"
 #include "ot_hit_list.hpp"
 
-#define OT_SPOT_THREADS 256
-#define OT_SPOT_WAVES (OT_SPOT_THREADS / 64)
 #define OT_SPOT_CHUNK 8  // frequencies per workgroup of pass 4: 32 f64 accumulators per lane
 // slots of the moments record (include/optrace_amd.h, ot_spot_moments)
 enum { SPOT_W = 0, SPOT_WX, SPOT_WY, SPOT_COUNT, SPOT_WDX2, SPOT_WDY2, SPOT_WDXDY, SPOT_R2MAX, SPOT_M };
-
-// v[0..M) of all lanes of the workgroup -> out[0..M), by thread m < M: sums, but the maximum for m == MAXI
-template <int M, int MAXI>
-OT_DEV void spot_block_reduce(double (&v)[M], double* __restrict__ out) {
-    static_assert(M <= OT_SPOT_THREADS, "one thread per quantity writes the partial");
-    __shared__ double sh[OT_SPOT_WAVES][M];
-    const bool first_lane = (threadIdx.x & 63) == 0;
-#pragma unroll
-    for (int m = 0; m < M; m++) {  // (stored as soon as folded: the 32 of pass 4 folded side by side spill under its 128-register cap)
-        double r = v[m];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double other = __shfl_down(r, o);
-            r = m == MAXI ? fmax(r, other) : r + other;
-        }
-        if (first_lane) sh[threadIdx.x >> 6][m] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < M) {
-        double r = sh[0][threadIdx.x];
-        for (int wv = 1; wv < OT_SPOT_WAVES; wv++) r = (int)threadIdx.x == MAXI ? fmax(r, sh[wv][threadIdx.x]) : r + sh[wv][threadIdx.x];
-        out[threadIdx.x] = r;
-    }
-}
 
 // part[gridDim.x][4]
 __global__ __launch_bounds__(OT_SPOT_THREADS) void spot_first_kernel(int64_t n, const double* __restrict__ x, const double* __restrict__ y,

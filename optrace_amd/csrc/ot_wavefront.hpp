@@ -1,0 +1,396 @@
+// Wavefront analysis of a traced bundle (Raytracer.wavefront_analysis): optical path to a reference sphere, its moments, a pupil
+// map and the normal equations of a Zernike fit, from the ray storage's planes.  Definition: DESIGN.md "Wavefront analysis".
+//   focus    sums for the point closest to all ray lines of section k and for the bundle's mean start and direction
+//   paths    per ray OPL = sum_{j<k} n_j |p_{j+1} - p_j| + n_k t to the sphere (centre c, signed radius R) and the pupil
+//            coordinates (u, v) of the intersection: four dense planes, w_out = 0 for rays that are not used
+//   moments  two passes over those planes: sums, then central sums about the means of the first
+//   map      sum w and sum w OPD per cell of an n_grid x n_grid pupil grid (f64 atomics)
+//   zernike  G = sum w Z Z^T (upper triangle) and g = sum w Z OPD for the Noll polynomials Z_1 .. Z_J
+// focus, moments and zernike add in the fixed order of ot_block_reduce.hpp and a last kernel over the workgroups' partials: two
+// calls return the same bits.  Every pass reads the results of those before it from device memory.
+// Defines kernels that are no templates: included by ot_wavefront_api.hip alone.
+#pragma once
+#include "ot_block_reduce.hpp"
+#include "ot_device.hpp"
+
+#define OT_WF_THREADS OT_SPOT_THREADS
+// slots of the focus record and the moments record (include/optrace_amd.h)
+enum { WFF_W = 0, WFF_COUNT, WFF_P, WFF_S = 5, WFF_A = 8, WFF_B = 14, WFF_M = 17 };
+enum { WF_W = 0, WF_COUNT, WF_WOPL, WF_WU, WF_WV, WF_WWL, WF_OPL_MIN, WF_OPL_MAX, WF_WOPD2, WF_R2MAX, WF_PUPIL_R, WF_M };
+
+// part[nblocks][M] -> out[M]: wave wv takes the quantities wv, wv + 4, ..., lane l the partials l, l + 64, ... in that order,
+// then the lanes fold as in the workgroups.  Bit m of maxmask: quantity m is a maximum; of negmask: it is stored negated (a
+// minimum carried as the maximum of the negated values).  One workgroup of four waves.
+__global__ __launch_bounds__(OT_WF_THREADS) void wf_final_kernel(const double* __restrict__ part, int nblocks, int M, unsigned maxmask,
+                                                                 unsigned negmask, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    for (int m = threadIdx.x >> 6; m < M; m += OT_SPOT_WAVES) {  // (wave-uniform)
+        const bool is_max = (maxmask >> m) & 1u;
+        double r = is_max ? -__builtin_inf() : 0.0;
+        for (int b = lane; b < nblocks; b += 64) {
+            const double p = part[(int64_t)M * b + m];
+            r = is_max ? fmax(r, p) : r + p;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double other = __shfl_down(r, o);
+            r = is_max ? fmax(r, other) : r + other;
+        }
+        if (lane == 0) out[m] = ((negmask >> m) & 1u) ? -r : r;
+    }
+}
+
+// ---- the rays of a section ------------------------------------------------------------------------------------------
+struct WfRay {
+    V3 p, s;  // start of the section and its direction, re-derived from the stored positions
+    double w;
+    bool used;  // w > 0 and a section of positive length
+};
+
+OT_DEV V3 wf_position(const ot_rays& R, int64_t r, int j) {
+    const int64_t N = R.N, nt = R.nt;
+    V3 p = {R.p[r + N * j], R.p[r + N * (j + nt)], R.p[r + N * (j + 2 * nt)]};
+    return p;
+}
+
+// (p0: the start of section k where the caller holds it already)
+OT_DEV WfRay wf_section(const ot_rays& R, int64_t r, int k, const V3& p0) {
+    WfRay q;
+    q.p = p0;
+    q.w = (double)R.w[r + R.N * k];
+    const V3 p1 = wf_position(R, r, k + 1);
+    const double dx = p1.x - p0.x, dy = p1.y - p0.y, dz = p1.z - p0.z;
+    const double L = ot_sqrt(dx * dx + dy * dy + dz * dz);
+    q.used = q.w > 0.0 && L > 0.0;
+    q.s.x = dx / L;
+    q.s.y = dy / L;
+    q.s.z = dz / L;
+    return q;
+}
+
+// part[gridDim.x][17]: W | count | sum w (p - origin) | sum w s | sum w (I - s s^T): xx xy xz yy yz zz | sum w (I - s s^T) (p - origin)
+__global__ __launch_bounds__(OT_WF_THREADS) void wf_focus_kernel(ot_rays R, int64_t first, int64_t count, int k, double ox, double oy,
+                                                                 double oz, double* __restrict__ part) {
+    double v[WFF_M];
+#pragma unroll
+    for (int m = 0; m < WFF_M; m++) v[m] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        const int64_t r = first + i;
+        const WfRay q = wf_section(R, r, k, wf_position(R, r, k));
+        if (!q.used) continue;
+        const double w = q.w, px = q.p.x - ox, py = q.p.y - oy, pz = q.p.z - oz;
+        const V3 s = q.s;
+        const double sp = s.x * px + s.y * py + s.z * pz;
+        v[WFF_W] += w;
+        v[WFF_COUNT] += 1.0;
+        v[WFF_P + 0] += w * px;
+        v[WFF_P + 1] += w * py;
+        v[WFF_P + 2] += w * pz;
+        v[WFF_S + 0] += w * s.x;
+        v[WFF_S + 1] += w * s.y;
+        v[WFF_S + 2] += w * s.z;
+        v[WFF_A + 0] += w * (1.0 - s.x * s.x);
+        v[WFF_A + 1] -= w * (s.x * s.y);
+        v[WFF_A + 2] -= w * (s.x * s.z);
+        v[WFF_A + 3] += w * (1.0 - s.y * s.y);
+        v[WFF_A + 4] -= w * (s.y * s.z);
+        v[WFF_A + 5] += w * (1.0 - s.z * s.z);
+        v[WFF_B + 0] += w * (px - s.x * sp);
+        v[WFF_B + 1] += w * (py - s.y * sp);
+        v[WFF_B + 2] += w * (pz - s.z * sp);
+    }
+    spot_block_reduce<WFF_M, -1>(v, part + WFF_M * (int64_t)blockIdx.x);
+}
+
+// The hot pass, one thread per ray of [first, first + count): (k + 2) positions and (k + 1) indices read plane by plane
+// (coalesced: neighbouring lanes, neighbouring rays), four dense planes written.  Rays that are not used leave NaN in u, v and
+// opl and 0 in w_out; those whose line misses the sphere are counted in `missed` besides.
+__global__ __launch_bounds__(OT_WF_THREADS) void wf_paths_kernel(ot_rays R, int64_t first, int64_t count, int k, double cx, double cy,
+                                                                 double cz, double radius, double* __restrict__ u, double* __restrict__ v,
+                                                                 double* __restrict__ opl, float* __restrict__ w_out,
+                                                                 unsigned long long* __restrict__ missed) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (i < count) {
+        const int64_t r = first + i, N = R.N;
+        const double nan = __builtin_nan("");
+        double ui = nan, vi = nan, li = nan;
+        float wi = 0.f;
+        if (R.w[r + N * k] > 0.f) {
+            V3 p0 = wf_position(R, r, 0);
+            double sum = 0.0;
+            for (int j = 0; j < k; j++) {  // ascending j, as the definition says
+                const V3 p1 = wf_position(R, r, j + 1);
+                const double dx = p1.x - p0.x, dy = p1.y - p0.y, dz = p1.z - p0.z;
+                sum += R.n[r + N * j] * ot_sqrt(dx * dx + dy * dy + dz * dz);
+                p0 = p1;
+            }
+            const WfRay q = wf_section(R, r, k, p0);
+            if (q.used) {
+                const double ax = fabs(radius), sg = radius > 0.0 ? 1.0 : -1.0;
+                const double qx = p0.x - cx, qy = p0.y - cy, qz = p0.z - cz;
+                const double b = q.s.x * qx + q.s.y * qy + q.s.z * qz;
+                const double c = (qx * qx + qy * qy + qz * qz) - radius * radius;
+                const double D = b * b - c;
+                if (D >= 0.0) {
+                    const double t = -b - sg * ot_sqrt(D);
+                    li = sum + R.n[r + N * k] * t;
+                    ui = (qx + t * q.s.x) / ax;
+                    vi = (qy + t * q.s.y) / ax;
+                    wi = (float)q.w;
+                } else {
+                    miss = true;  // (a NaN discriminant too: the ray has no place on the sphere)
+                }
+            }
+        }
+        u[i] = ui;
+        v[i] = vi;
+        opl[i] = li;
+        w_out[i] = wi;
+    }
+    const unsigned long long m = __ballot(miss);
+    if (__lane_id() == 0 && m) atomicAdd(missed, (unsigned long long)__popcll(m));
+}
+
+// ---- moments of the planes -------------------------------------------------------------------------------------------
+// part[gridDim.x][8]: the first eight slots of the record, the minimum as the maximum of -opl
+__global__ __launch_bounds__(OT_WF_THREADS) void wf_first_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
+                                                                 const double* __restrict__ opl, const float* __restrict__ w,
+                                                                 const float* __restrict__ wl, double* __restrict__ part) {
+    const double inf = __builtin_inf();
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -inf, -inf};
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float wi = w[i];
+        if (!(wi > 0.f)) continue;
+        const double wd = (double)wi, l = opl[i];
+        a[WF_W] += wd;
+        a[WF_COUNT] += 1.0;
+        a[WF_WOPL] += wd * l;
+        a[WF_WU] += wd * u[i];
+        a[WF_WV] += wd * v[i];
+        if (wl) a[WF_WWL] += wd * (double)wl[i];
+        a[WF_OPL_MIN] = fmax(a[WF_OPL_MIN], -l);
+        a[WF_OPL_MAX] = fmax(a[WF_OPL_MAX], l);
+    }
+    spot_block_reduce<8, WF_OPL_MIN, WF_OPL_MAX>(a, part + 8 * (int64_t)blockIdx.x);
+}
+
+// the means every later pass subtracts: the same IEEE quotients as the host forms from the record
+struct WfMeans {
+    double opl, u, v;
+};
+OT_DEV WfMeans wf_means(const double* __restrict__ mom) { return {mom[WF_WOPL] / mom[WF_W], mom[WF_WU] / mom[WF_W], mom[WF_WV] / mom[WF_W]}; }
+
+// part[gridDim.x][2]: sum w opd^2 | max (du^2 + dv^2)
+__global__ __launch_bounds__(OT_WF_THREADS) void wf_central_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
+                                                                   const double* __restrict__ opl, const float* __restrict__ w,
+                                                                   const double* __restrict__ mom, double* __restrict__ part) {
+    const WfMeans c = wf_means(mom);
+    double a[2] = {0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float wi = w[i];
+        if (!(wi > 0.f)) continue;
+        const double d = opl[i] - c.opl, du = u[i] - c.u, dv = v[i] - c.v;
+        a[0] += (double)wi * (d * d);
+        a[1] = fmax(a[1], du * du + dv * dv);
+    }
+    spot_block_reduce<2, 1>(a, part + 2 * (int64_t)blockIdx.x);
+}
+
+// The pupil radius the later passes divide by when the caller gives none, stored so that the host reports this very number
+__global__ void wf_pupil_radius_kernel(double* __restrict__ mom) { mom[WF_PUPIL_R] = ot_sqrt(mom[WF_R2MAX]); }
+
+// Unit-disc coordinates of an entry.  pupil_radius NaN: the largest distance from the pupil centre (moments), every entry
+// inside; otherwise the caller's, and entries beyond it are left out.  All entries in one place: the centre of the disc.
+struct WfPupil {
+    double cu, cv, radius;
+    bool given;
+};
+OT_DEV WfPupil wf_pupil(const double* __restrict__ mom, double pupil_radius) {
+    const WfMeans c = wf_means(mom);
+    const bool given = pupil_radius == pupil_radius;
+    return {c.u, c.v, given ? pupil_radius : mom[WF_PUPIL_R], given};
+}
+OT_DEV bool wf_unit_disc(const WfPupil& P, double u, double v, double* x, double* y) {
+    const bool spread = P.radius > 0.0;
+    *x = spread ? (u - P.cu) / P.radius : 0.0;
+    *y = spread ? (v - P.cv) / P.radius : 0.0;
+    return !(P.given && *x * *x + *y * *y > 1.0);
+}
+
+// map[2][n_grid][n_grid] += w | w opd, row = cell of y, column = cell of x, cell = min(floor((x + 1) / 2 n_grid), n_grid - 1).
+// LDS-privatised when the sums fit (lds_cells = 2 n_grid^2), otherwise global atomics.
+__global__ __launch_bounds__(1024) void wf_map_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
+                                                      const double* __restrict__ opl, const float* __restrict__ w,
+                                                      const double* __restrict__ mom, double pupil_radius, int n_grid, int lds_cells,
+                                                      double* __restrict__ map) {
+    extern __shared__ double sh[];  // [lds_cells] sums
+    if (lds_cells) {
+        for (int i = threadIdx.x; i < lds_cells; i += blockDim.x) sh[i] = 0.0;
+        __syncthreads();
+    }
+    const WfPupil P = wf_pupil(mom, pupil_radius);
+    const double mean = wf_means(mom).opl, fn = (double)n_grid;
+    const int64_t cells = (int64_t)n_grid * n_grid;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float wi = w[i];
+        if (!(wi > 0.f)) continue;
+        double x, y;
+        if (!wf_unit_disc(P, u[i], v[i], &x, &y)) continue;
+        const double qx = floor((x + 1.0) / 2.0 * fn), qy = floor((y + 1.0) / 2.0 * fn);
+        // (x >= -1 up to rounding: a value an ulp outside, or no number at all, must not index outside the map)
+        const int ix = !(qx >= 0.0) ? 0 : qx < fn - 1.0 ? (int)qx : n_grid - 1;
+        const int iy = !(qy >= 0.0) ? 0 : qy < fn - 1.0 ? (int)qy : n_grid - 1;
+        const int64_t cell = (int64_t)iy * n_grid + ix;
+        const double wd = (double)wi, wo = wd * (opl[i] - mean);
+        if (lds_cells) {
+            unsafeAtomicAdd(&sh[cell], wd);
+            unsafeAtomicAdd(&sh[cells + cell], wo);
+        } else {
+            unsafeAtomicAdd(&map[cell], wd);
+            unsafeAtomicAdd(&map[cells + cell], wo);
+        }
+    }
+    if (lds_cells) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < lds_cells; i += blockDim.x) {
+            const double s = sh[i];
+            if (s != 0.0) unsafeAtomicAdd(&map[i], s);
+        }
+    }
+}
+
+// ---- Zernike polynomials, Noll's order -------------------------------------------------------------------------------
+// Z_j = N_n^m R_n^|m|(rho) cos(m theta) for even j, sin(|m| theta) for odd j, 1 for m = 0.  rho^m cos / sin (m theta) are the
+// real and imaginary parts of (x + i y)^m, and R_n^m / rho^m is a polynomial in rho^2 whose coefficients, times the norm, are
+// compile-time constants: no trigonometry, no division, no special case at the centre.
+constexpr int wf_noll_n(int j) {  // radial order of Z_j, j from 1
+    int n = 0;
+    while ((n + 1) * (n + 2) / 2 < j) n++;
+    return n;
+}
+constexpr int wf_noll_m(int j) {  // azimuthal order |m|
+    const int n = wf_noll_n(j), p = j - n * (n + 1) / 2 - 1;
+    return n % 2 ? 2 * (p / 2) + 1 : 2 * ((p + 1) / 2);
+}
+constexpr double wf_factorial(int k) { return k < 2 ? 1.0 : k * wf_factorial(k - 1); }
+// coefficient of rho^(n - 2 i) in R_n^m
+constexpr double wf_radial_coeff(int n, int m, int i) {
+    return (i % 2 ? -1.0 : 1.0) * wf_factorial(n - i) / (wf_factorial(i) * wf_factorial((n + m) / 2 - i) * wf_factorial((n - m) / 2 - i));
+}
+// sqrt(n + 1) and sqrt(2 n + 2), n = 0 .. 7
+constexpr double wf_norm0[8] = {1.0, 1.4142135623730951, 1.7320508075688772, 2.0, 2.23606797749979, 2.449489742783178,
+                                2.6457513110645907, 2.8284271247461903};
+constexpr double wf_normm[8] = {1.4142135623730951, 2.0, 2.449489742783178, 2.8284271247461903, 3.1622776601683795,
+                                3.4641016151377544, 3.7416573867739413, 4.0};
+
+template <int J>
+struct WfZernikeTerm {
+    static constexpr int n = wf_noll_n(J), m = wf_noll_m(J), deg = (n - m) / 2;
+    static constexpr double norm = m ? wf_normm[n] : wf_norm0[n];
+    // norm times the coefficients of R_n^m / rho^m, highest power of t = rho^2 first (at most four: n <= 7); constants of the
+    // class, so that the compiler holds numbers and no calls
+    static constexpr double c0 = norm * wf_radial_coeff(n, m, 0), c1 = deg >= 1 ? norm * wf_radial_coeff(n, m, 1) : 0.0,
+                            c2 = deg >= 2 ? norm * wf_radial_coeff(n, m, 2) : 0.0, c3 = deg >= 3 ? norm * wf_radial_coeff(n, m, 3) : 0.0;
+    static_assert(deg <= 3, "radial orders up to 7");
+    // cm[i], sm[i]: real and imaginary part of (x + i y)^i; t = x^2 + y^2
+    static OT_DEV double eval(const double (&cm)[8], const double (&sm)[8], double t) {
+        double r = c0;
+        if constexpr (deg >= 1) r = r * t + c1;
+        if constexpr (deg >= 2) r = r * t + c2;
+        if constexpr (deg >= 3) r = r * t + c3;
+        return r * (m == 0 ? 1.0 : J % 2 ? sm[m] : cm[m]);
+    }
+};
+template <int JT, int J = 1>
+struct WfZernikeAll {
+    static OT_DEV void eval(double (&Z)[JT], const double (&cm)[8], const double (&sm)[8], double t) {
+        Z[J - 1] = WfZernikeTerm<J>::eval(cm, sm, t);
+        if constexpr (J < JT) WfZernikeAll<JT, J + 1>::eval(Z, cm, sm, t);
+    }
+};
+template <int JT>
+OT_DEV void wf_zernike_all(double x, double y, double (&Z)[JT]) {
+    double cm[8], sm[8];
+    cm[0] = 1.0;
+    sm[0] = 0.0;
+#pragma unroll
+    for (int i = 1; i < 8; i++) {
+        cm[i] = cm[i - 1] * x - sm[i - 1] * y;
+        sm[i] = cm[i - 1] * y + sm[i - 1] * x;
+    }
+    WfZernikeAll<JT>::eval(Z, cm, sm, x * x + y * y);
+}
+
+// Normal equations for the first JT polynomials, JT the table size at or above the caller's J.  Workgroup (bx, c) walks the list
+// as workgroup bx of gridDim.x for chunk c < (JT + 1) / 2: rows a = c and b = JT - 1 - c of the upper triangle, JT + 1 entries of
+// G between them, and their two entries of g.  Slot s of the JT + 3 accumulators per lane:
+//   s >= c      G[a][s]             s < c   G[b][JT - 1 - s]          s = JT  G[b][b]       JT + 1, JT + 2   g[a], g[b]
+// (a = b in the middle chunk of an odd JT: its slots s < c, JT and JT + 2 repeat others of the chunk and are dropped).  Every Z index but
+// a and b is a compile-time one, so Z and the accumulators stay in registers.  part[gridDim.x][gridDim.y][JT + 3].
+template <int JT>
+__global__ __launch_bounds__(OT_WF_THREADS) void wf_zernike_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
+                                                                   const double* __restrict__ opl, const float* __restrict__ w,
+                                                                   const double* __restrict__ mom, double pupil_radius,
+                                                                   double* __restrict__ part) {
+    constexpr int S = JT + 3;
+    const WfPupil P = wf_pupil(mom, pupil_radius);
+    const double mean = wf_means(mom).opl;
+    const int c = blockIdx.y;
+    double acc[S];
+#pragma unroll
+    for (int s = 0; s < S; s++) acc[s] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float wi = w[i];
+        if (!(wi > 0.f)) continue;
+        double x, y;
+        if (!wf_unit_disc(P, u[i], v[i], &x, &y)) continue;
+        double Z[JT];
+        wf_zernike_all<JT>(x, y, Z);
+        double za = Z[0], zb = Z[JT - 1];
+#pragma unroll
+        for (int s = 1; s < (JT + 1) / 2; s++) {  // (wave-uniform selects)
+            za = s == c ? Z[s] : za;
+            zb = s == c ? Z[JT - 1 - s] : zb;
+        }
+        const double wd = (double)wi, wa = wd * za, wb = wd * zb;
+#pragma unroll
+        for (int s = 0; s < JT; s++) acc[s] += s >= c ? wa * Z[s] : wb * Z[JT - 1 - s];
+        acc[JT] += wb * zb;
+        const double opd = opl[i] - mean;
+        acc[JT + 1] += wa * opd;
+        acc[JT + 2] += wb * opd;
+    }
+    spot_block_reduce<S, -1>(acc, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * S);
+}
+
+// part[nblocks][chunks][JT + 3] -> out: G's upper triangle row by row (i <= j < J), then g[J].  One thread per slot of a chunk
+// adds its partials in index order and stores the sum where its (i, j) belongs, if that lies within J.
+__global__ __launch_bounds__(OT_WF_THREADS) void wf_zernike_final_kernel(const double* __restrict__ part, int nblocks, int JT, int J,
+                                                                         double* __restrict__ out) {
+    const int S = JT + 3, chunks = (JT + 1) / 2;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= chunks * S) return;
+    const int c = q / S, s = q % S, a = c, b = JT - 1 - c;
+    int i, j;  // j = -1: an entry of g
+    if (s < JT) {
+        i = s >= c ? a : b;
+        j = s >= c ? s : JT - 1 - s;
+    } else if (s == JT) {
+        i = j = b;
+    } else {
+        i = s == JT + 1 ? a : b;
+        j = -1;
+    }
+    if (a == b && (s < c || s == JT || s == JT + 2)) return;  // the middle chunk's repeats
+    if (i >= J || j >= J) return;
+    double r = 0.0;
+    for (int k = 0; k < nblocks; k++) r += part[((int64_t)k * chunks + c) * S + s];
+    const int tri = J * (J + 1) / 2;
+    out[j < 0 ? tri + i : i * J - i * (i - 1) / 2 + (j - i)] = r;
+}

@@ -24,7 +24,7 @@ import torch
 from . import _capi
 from . import base as _base
 from .base import check_type
-from .geometry.elements import Group, Aperture, Detector
+from .geometry.elements import Group, Aperture, Detector, Lens, Filter
 from .geometry.surfaces import Surface, Point, Line, SphericalSurface, RingSurface, SlitSurface
 from .options import global_options
 from .ray_storage import RayStorage, TailStorage, SceneRef
@@ -33,6 +33,8 @@ from .render_image import RenderImage
 from .spectrum import LightSpectrum
 from . import spot as _spot
 from .spot import SpotAnalysis
+from . import wavefront as _wavefront
+from .wavefront import WavefrontAnalysis
 from .geometry.ray_source import RaySource
 from .scene import CompiledScene, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
@@ -804,6 +806,40 @@ class Raytracer(Group):
                            long_desc="Spot at " + rq.image_label)
         self._warn_ill(hits.ill_count, detector_index)
         return sa
+
+    def wavefront_analysis(self, source_index: int = 0, section: int = None, focus=None, radius: float = None,
+                           n_zernike: int = 15, n_grid: int = 64, pupil_radius: float = None) -> WavefrontAnalysis:
+        """Optical path difference of one source's rays (None: all rays) against a reference sphere, its RMS and
+        peak-to-valley, Zernike coefficients and a pupil map (no counterpart in optrace): reductions over the stored sections
+        on the GPU (wavefront.py).  section: the ray section whose lines meet the sphere, default the space behind the last
+        surface; focus, radius: centre and signed radius of the sphere, default the point closest to all ray lines and its
+        distance from the mean start of the section; n_zernike: Noll polynomials fitted; n_grid: cells per side of the map;
+        pupil_radius: radius of the unit disc in units of |radius|, default the largest distance from the pupil centre."""
+        surfaces = self.tracing_surfaces
+        nt = len(surfaces) + 2
+        focus, radius, pupil_radius = _wavefront.check_arguments(nt, section, focus, radius, n_zernike, n_grid, pupil_radius)
+        if source_index is not None:
+            check_type("source_index", source_index, int)
+        require_device()  # (said before anything about the rays: without a device there are none)
+        if not self.ray_sources:
+            raise RuntimeError("Ray Sources Missing.")
+        self._need_rays()
+        Ns, Ne = self._ray_range(source_index)
+        self._need_current()
+        k = nt - 2 if section is None else section
+        # surface i of the geometry ends section i: those before section k are the surfaces 0 .. k - 1
+        i = 0
+        for el in self.elements:
+            if isinstance(el, (Lens, Filter, Aperture)):
+                if i < k and getattr(el, "is_ideal", False):
+                    warning(f"An ideal lens lies before section {k}: the optical path through an ideal lens is not defined, "
+                            "the wavefront figures hold up to what it would add.")
+                    break
+                i += 1 if el.back is None or getattr(el, "is_ideal", False) else 2
+        origin = surfaces[k - 1].pos if k else self.ray_sources[source_index or 0].pos
+        label = "all rays" if source_index is None else f"{RaySource.abbr}{source_index}"
+        return _wavefront.analyse(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_zernike, n_grid, pupil_radius,
+                                  long_desc=f"Wavefront of {label} behind section {k}")
 
     # ---- source side (raytracer.py:1281-1352) ---------------------------------------------------------------
     def _hit_source(self, info: str, source_index: int = 0):
