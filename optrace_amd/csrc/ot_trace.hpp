@@ -51,7 +51,8 @@ OT_DEV void compute_polarization(const V3& s, const V3& s_, const RayState& r, f
     }
     bool mask = (s.x != s_.x) || (s.y != s_.y) || (s.z != s_.z);
     V3 ps = cross3(s_, s);
-    double inv = rsqrt(ps.x * ps.x + ps.y * ps.y + ps.z * ps.z);
+    const double l2 = ps.x * ps.x + ps.y * ps.y + ps.z * ps.z;
+    double inv = rsqrt(l2);
     ps.x *= inv;
     ps.y *= inv;
     ps.z *= inv;
@@ -68,6 +69,25 @@ OT_DEV void compute_polarization(const V3& s, const V3& s_, const RayState& r, f
         npx = (float)(ps.x * A_ts + pp_.x * A_tp);
         npy = (float)(ps.y * A_ts + pp_.y * A_tp);
         npz = (float)(ps.z * A_ts + pp_.z * A_tp);
+    }
+    // A small bend (HURB through a wide opening or with small draws, an ideal lens near its centre): s' x s carries
+    // ~2^-53 absolute against a length a = |s' x s|, and the part of that error along s tilts ps out of the plane
+    // perpendicular to s, so pol' is off by ~2^-53 / a along s (measured 2.7e-3 at a = 2^-48; the reference's own form is
+    // as noisy, tests/test_hurb_host.py).  With t the unit vector of s' - s, the projection is exactly
+    //     pol' = pol - s (s'.pol) - (1 - cos theta) [t (t.pol) + s (s.pol)],
+    // and the last term is below a^2 / 2: under a = 2^-20 the first two are pol' to 2^-41, without any basis.  (At 2^-20
+    // the basis form is good to 2^-33: either side of the threshold is far inside the float32 store.)  A_ts and A_tp
+    // are not used by the callers that can get here (refract_ideal, hurb_bend: no Fresnel factor).  One comparison on the
+    // common path; the rest sits behind a wave-uniform branch that the waves of an ordinary bundle skip (computed for
+    // every lane it cost the render-only C5 kernel 2 %).
+    const bool small = mask && l2 < 0x1p-40;
+    if (__ballot(small) != 0ull) {
+        if (small) {
+            const double sp = dot3(s_, pol);
+            npx = (float)(pol.x - s.x * sp);
+            npy = (float)(pol.y - s.y * sp);
+            npz = (float)(pol.z - s.z * sp);
+        }
     }
 }
 
