@@ -771,6 +771,31 @@ int ot_wavefront_map(int64_t n, const double* u, const double* v, const double* 
 int ot_wavefront_zernike(int64_t n, const double* u, const double* v, const double* opl, const float* w, const double* moments,
                          double pupil_radius, int32_t J, double* workspace, double* out, void* stream);
 
+/* ---- Huygens point spread function (Raytracer.huygens_psf; no counterpart in optrace) -----------------------------
+ * The coherent sum of one spherical wavelet per ray over the points of an image plane, from the rays' places and optical
+ * paths on the reference sphere of the wavefront analysis above.  Pointers are DEVICE unless said otherwise; launches are
+ * ordered on `stream` and nothing is waited for.  Bad arguments: OT_ERR_INVALID, n_px above OT_PSF_MAX_PX:
+ * OT_ERR_UNSUPPORTED, both before a device is looked for; count = 0 / n = 0 returns OT_OK without a launch.
+ * ot_psf_rays: rec[OT_PSF_REC * count], six planes of `count` entries: q (3) = (p[section] + t s - focus) / |radius|, the
+ *   ray's place on the sphere by the step of ot_wavefront_paths (focus[3] HOST) | tau0 = (opl - mean) / lambda, turns, with
+ *   opl[count] as ot_wavefront_paths wrote it, its mean moments[2] / moments[0] of ot_wavefront_moments and lambda = 1e-6 wl
+ *   in mm | kappa = n[section] / lambda | a = sqrt(w[section]).  Rays that ot_wavefront_paths does not use: six zeros.
+ *   Reads p, w, n and wl.
+ * ot_psf_sum: with delta = x - focus, h = |radius| q and sg = sign(radius), U(x) = sum_i a_i exp(2 pi i tau_i),
+ *   tau_i = tau0_i + sg kappa_i (|delta - h_i| - |radius|), the difference formed as
+ *   (delta . delta - 2 |radius| delta . q) / (|delta - h| + |radius|).  field[2 * n_px * n_px] = Re U | Im U at the points
+ *   delta = ((column + 1/2 - n_px / 2) size / n_px, (row + 1/2 - n_px / 2) size / n_px, dz), index row * n_px + column;
+ *   centre[4] = Re U, Im U at delta = (0, 0, dz) | sum a | sum a^2.  1 <= n_px <= OT_PSF_MAX_PX, size finite and above
+ *   zero, dz finite, radius finite and not zero.  workspace >= ot_psf_workspace(n, n_px) doubles (0 for arguments out of
+ *   range).  The rays are added in an order fixed by n and n_px alone: the same call returns the same bits. */
+#define OT_PSF_MAX_PX 1024
+#define OT_PSF_REC 6
+int64_t ot_psf_workspace(int64_t n, int32_t n_px);
+int ot_psf_rays(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const double* focus, double radius,
+                const double* opl, const double* moments, double* rec, void* stream);
+int ot_psf_sum(int64_t n, const double* rec, double radius, int32_t n_px, double size, double dz, double* workspace, double* field,
+               double* centre, void* stream);
+
 /* ---- samplers: optrace/tracer/random.py, Surface.random_positions, color.random_wavelengths_from_srgb ---------
  * The samplers of the ray generator (ot_rays_generate) as entry points of their own: sample i of a call is what the
  * generator draws for ray i of a launch with the same seed and the same ranges -- counter-based dither keyed by (seed, i),

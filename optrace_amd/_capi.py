@@ -196,6 +196,9 @@ SIGNATURES = {
     "ot_wavefront_moments": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ot_wavefront_map": (C.c_int, [i64, vp, vp, vp, vp, vp, C.c_double, i32, vp, vp]),
     "ot_wavefront_zernike": (C.c_int, [i64, vp, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp]),
+    "ot_psf_workspace": (i64, [i64, i32]),
+    "ot_psf_rays": (C.c_int, [C.POINTER(Rays), i64, i64, i32, C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp]),
+    "ot_psf_sum": (C.c_int, [i64, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, vp]),
     "ot_sample_stratified": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(SourceRange), i32, u64, i64, vp, vp, vp]),
     "ot_sample_positions": (C.c_int, [C.POINTER(Source), C.POINTER(SourceRange), i32, u64, i64, vp, vp]),
     "ot_sample_inverse": (C.c_int, [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i64, vp, i64, C.POINTER(SourceRange), i32,
@@ -215,11 +218,24 @@ SAMPLE_INTERVAL, SAMPLE_RECTANGLE, SAMPLE_RING = range(3)  # OT_SAMPLE_*
 SAMPLE_DISCRETE, SAMPLE_CONTINUOUS = range(2)
 SPOT_M, SPOT_MAX_RADII, SPOT_MAX_FREQ = 8, 65536, 4096  # OT_SPOT_*
 WF_FOCUS_M, WF_M, WF_MAX_J, WF_MAX_GRID, WF_WS = 17, 11, 36, 1024, 40 * 2048  # OT_WF_*
+PSF_MAX_PX, PSF_REC = 1024, 6  # OT_PSF_*
 
 
 def spot_ws(K: int) -> int:
     """OT_SPOT_WS(K): doubles of workspace for ot_spot_moments (K = 0) and ot_spot_otf."""
     return 32 * 2048 + 256 * (K + 8)
+
+
+
+def psf_ws(n: int, n_px: int) -> int:
+    """ot_psf_workspace(n, n_px): doubles of workspace for ot_psf_sum.  The image points and the one on the axis go in tiles of 1024
+    to workgroups, of which about 1024 are aimed at; the rays go in as many chunks as that leaves, of 128 rays at least.  Per chunk:
+    Re and Im of every point, sum a and sum a^2."""
+    points = n_px * n_px + 1
+    tiles = -(-points // 1024)
+    chunks = max(1, min(1024 // tiles, -(-n // 128)))
+    return chunks * (2 * points + 2)
+
 
 _lib = None
 

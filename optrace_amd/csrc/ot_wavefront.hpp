@@ -12,11 +12,9 @@
 #pragma once
 #include "ot_block_reduce.hpp"
 #include "ot_device.hpp"
+#include "ot_wavefront_ray.hpp"  // the rays of a section, their sphere step, the slots of the records
 
 #define OT_WF_THREADS OT_SPOT_THREADS
-// slots of the focus record and the moments record (include/optrace_amd.h)
-enum { WFF_W = 0, WFF_COUNT, WFF_P, WFF_S = 5, WFF_A = 8, WFF_B = 14, WFF_M = 17 };
-enum { WF_W = 0, WF_COUNT, WF_WOPL, WF_WU, WF_WV, WF_WWL, WF_OPL_MIN, WF_OPL_MAX, WF_WOPD2, WF_R2MAX, WF_PUPIL_R, WF_M };
 
 // part[nblocks][M] -> out[M]: wave wv takes the quantities wv, wv + 4, ..., lane l the partials l, l + 64, ... in that order,
 // then the lanes fold as in the workgroups.  Bit m of maxmask: quantity m is a maximum; of negmask: it is stored negated (a
@@ -38,34 +36,6 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_final_kernel(const double* _
         }
         if (lane == 0) out[m] = ((negmask >> m) & 1u) ? -r : r;
     }
-}
-
-// ---- the rays of a section ------------------------------------------------------------------------------------------
-struct WfRay {
-    V3 p, s;  // start of the section and its direction, re-derived from the stored positions
-    double w;
-    bool used;  // w > 0 and a section of positive length
-};
-
-OT_DEV V3 wf_position(const ot_rays& R, int64_t r, int j) {
-    const int64_t N = R.N, nt = R.nt;
-    V3 p = {R.p[r + N * j], R.p[r + N * (j + nt)], R.p[r + N * (j + 2 * nt)]};
-    return p;
-}
-
-// (p0: the start of section k where the caller holds it already)
-OT_DEV WfRay wf_section(const ot_rays& R, int64_t r, int k, const V3& p0) {
-    WfRay q;
-    q.p = p0;
-    q.w = (double)R.w[r + R.N * k];
-    const V3 p1 = wf_position(R, r, k + 1);
-    const double dx = p1.x - p0.x, dy = p1.y - p0.y, dz = p1.z - p0.z;
-    const double L = ot_sqrt(dx * dx + dy * dy + dz * dz);
-    q.used = q.w > 0.0 && L > 0.0;
-    q.s.x = dx / L;
-    q.s.y = dy / L;
-    q.s.z = dz / L;
-    return q;
 }
 
 // part[gridDim.x][17]: W | count | sum w (p - origin) | sum w s | sum w (I - s s^T): xx xy xz yy yz zz | sum w (I - s s^T) (p - origin)
@@ -126,23 +96,15 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_paths_kernel(ot_rays R, int6
                 sum += R.n[r + N * j] * ot_sqrt(dx * dx + dy * dy + dz * dz);
                 p0 = p1;
             }
-            const WfRay q = wf_section(R, r, k, p0);
-            if (q.used) {
-                const double ax = fabs(radius), sg = radius > 0.0 ? 1.0 : -1.0;
-                const double qx = p0.x - cx, qy = p0.y - cy, qz = p0.z - cz;
-                const double b = q.s.x * qx + q.s.y * qy + q.s.z * qz;
-                const double c = (qx * qx + qy * qy + qz * qz) - radius * radius;
-                const double D = b * b - c;
-                if (D >= 0.0) {
-                    const double t = -b - sg * ot_sqrt(D);
-                    li = sum + R.n[r + N * k] * t;
-                    ui = (qx + t * q.s.x) / ax;
-                    vi = (qy + t * q.s.y) / ax;
-                    wi = (float)q.w;
-                } else {
-                    miss = true;  // (a NaN discriminant too: the ray has no place on the sphere)
-                }
+            const WfSphere h = wf_sphere(R, r, k, p0, cx, cy, cz, radius);
+            if (h.hit) {
+                const double ax = fabs(radius);
+                li = sum + R.n[r + N * k] * h.t;
+                ui = h.h.x / ax;
+                vi = h.h.y / ax;
+                wi = (float)h.w;
             }
+            miss = h.used && !h.hit;
         }
         u[i] = ui;
         v[i] = vi;
@@ -176,12 +138,6 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_first_kernel(int64_t n, cons
     }
     spot_block_reduce<8, WF_OPL_MIN, WF_OPL_MAX>(a, part + 8 * (int64_t)blockIdx.x);
 }
-
-// the means every later pass subtracts: the same IEEE quotients as the host forms from the record
-struct WfMeans {
-    double opl, u, v;
-};
-OT_DEV WfMeans wf_means(const double* __restrict__ mom) { return {mom[WF_WOPL] / mom[WF_W], mom[WF_WU] / mom[WF_W], mom[WF_WV] / mom[WF_W]}; }
 
 // part[gridDim.x][2]: sum w opd^2 | max (du^2 + dv^2)
 __global__ __launch_bounds__(OT_WF_THREADS) void wf_central_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,

@@ -35,6 +35,8 @@ from . import spot as _spot
 from .spot import SpotAnalysis
 from . import wavefront as _wavefront
 from .wavefront import WavefrontAnalysis
+from . import psf as _psf
+from .psf import HuygensPSF
 from .geometry.ray_source import RaySource
 from .scene import CompiledScene, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
@@ -815,9 +817,31 @@ class Raytracer(Group):
         surface; focus, radius: centre and signed radius of the sphere, default the point closest to all ray lines and its
         distance from the mean start of the section; n_zernike: Noll polynomials fitted; n_grid: cells per side of the map;
         pupil_radius: radius of the unit disc in units of |radius|, default the largest distance from the pupil centre."""
+        nt = len(self.tracing_surfaces) + 2
+        focus, radius, pupil_radius = _wavefront.check_arguments(nt, section, focus, radius, n_zernike, n_grid, pupil_radius)
+        Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the wavefront figures hold")
+        return _wavefront.analyse(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_zernike, n_grid, pupil_radius,
+                                  long_desc=f"Wavefront of {label} behind section {k}")
+
+    def huygens_psf(self, source_index: int = 0, section: int = None, focus=None, radius: float = None, n_px: int = 64,
+                    size: float = None, dz: float = 0.0) -> HuygensPSF:
+        """Diffraction image of a point from one source's rays (None: all rays), no counterpart in optrace: every ray sends a
+        spherical wavelet from its place on the reference sphere of `wavefront_analysis`, with the phase of its optical path, and
+        the wavelets are added coherently on the GPU (psf.py).  section, focus, radius: as for `wavefront_analysis`; n_px: image
+        points per side; size: side length of the square of image points about the focus in the plane z = focus z + dz, default
+        ten mean wavelengths over the pupil radius (about eight Airy diameters in air)."""
+        nt = len(self.tracing_surfaces) + 2
+        focus, radius, size, dz = _psf.check_arguments(nt, section, focus, radius, n_px, size, dz)
+        Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the point spread function holds")
+        return _psf.analyse(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_px, size, dz,
+                            long_desc=f"Huygens PSF of {label} behind section {k}")
+
+    def _section_bundle(self, source_index, section, holds: str):
+        """What the analyses of a stored section share, after their own argument checks: the device, current rays, the ray range
+        of the source, the section (default: the space behind the last surface), a point near its start and a label.  Warns of
+        an ideal lens before the section.  -> (Ns, Ne, k, origin, label)"""
         surfaces = self.tracing_surfaces
         nt = len(surfaces) + 2
-        focus, radius, pupil_radius = _wavefront.check_arguments(nt, section, focus, radius, n_zernike, n_grid, pupil_radius)
         if source_index is not None:
             check_type("source_index", source_index, int)
         require_device()  # (said before anything about the rays: without a device there are none)
@@ -833,13 +857,12 @@ class Raytracer(Group):
             if isinstance(el, (Lens, Filter, Aperture)):
                 if i < k and getattr(el, "is_ideal", False):
                     warning(f"An ideal lens lies before section {k}: the optical path through an ideal lens is not defined, "
-                            "the wavefront figures hold up to what it would add.")
+                            f"{holds} up to what it would add.")
                     break
                 i += 1 if el.back is None or getattr(el, "is_ideal", False) else 2
         origin = surfaces[k - 1].pos if k else self.ray_sources[source_index or 0].pos
         label = "all rays" if source_index is None else f"{RaySource.abbr}{source_index}"
-        return _wavefront.analyse(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_zernike, n_grid, pupil_radius,
-                                  long_desc=f"Wavefront of {label} behind section {k}")
+        return Ns, Ne, k, origin, label
 
     # ---- source side (raytracer.py:1281-1352) ---------------------------------------------------------------
     def _hit_source(self, info: str, source_index: int = 0):
