@@ -798,14 +798,9 @@ static int spectrum_histogram(int64_t n, const unsigned int* fill, const float* 
     if (int rc = require_device()) return rc;
     if (n == 0) return OT_OK;
     hipStream_t st = (hipStream_t)stream;
-    // sums (f64) + edges (f32) per workgroup; 64 KiB keeps two workgroups of LDS per CU free for other work
-    const size_t lds = (size_t)nbins * sizeof(double) + ((size_t)nbins + 2) * sizeof(float);
-    const int lds_bins = lds <= 64 * 1024 ? nbins : 0;
-    int64_t blocks = (n + 1023) / 1024;
-    const int64_t cap = cu_count();
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(spectrum_hist_kernel, dim3((unsigned)blocks), dim3(1024), lds_bins ? lds : 0, st, n, wl, w, edges,
-                       nbins, lds_bins, hist, fill);
+    // sums (f64) + edges (f32) per workgroup
+    const HistShape hs = hist_shape(n, (size_t)nbins * sizeof(double) + ((size_t)nbins + 2) * sizeof(float));
+    hipLaunchKernelGGL(spectrum_hist_kernel, hs.grid, hs.block, hs.lds, st, n, wl, w, edges, nbins, hs.lds ? nbins : 0, hist, fill);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }

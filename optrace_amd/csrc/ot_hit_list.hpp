@@ -1,6 +1,7 @@
 // Hit lists behind the detector stage: their layout and the index walk of the kernels that stream them (spectrum, spot
-// analysis).  A list is dense (one entry per ray of the bundle, weight 0 = no valid hit, as ot_detector_hits leaves it) or
-// compact (ot_detector_req.fill: 1024 pieces of hit_piece_len(n) entries, piece k holding fill[k] valid hits at its front).
+// analysis; the wavefront analysis walks its planes as a dense list).  A list is dense (one entry per ray of the bundle,
+// weight 0 = no valid hit, as ot_detector_hits leaves it) or compact (ot_detector_req.fill: 1024 pieces of hit_piece_len(n)
+// entries, piece k holding fill[k] valid hits at its front).
 // Holds no kernels: any unit may include it.
 #pragma once
 #include "ot_device.hpp"
@@ -17,14 +18,21 @@ __host__ __device__ static inline int64_t hit_piece_len(int64_t n) { return (int
 
 #define OT_HIT_SLICE 8192  // entries of a compact list a workgroup takes at a time
 
-// body(i) for the entries of a list: dense = grid-stride over [0, n); compact = the workgroup takes whole slices of pieces.
+// body(i) for i in [0, n), grid-stride: the walk of a dense list, and of the dense planes of the wavefront analysis.  `return`
+// in the body goes on to the next entry.
+template <class F>
+OT_DEV void dense_for_each(int64_t n, F&& body) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) body(i);
+}
+
+// body(i) for the entries of a list: dense = dense_for_each; compact = the workgroup takes whole slices of pieces.
 // Which workgroup and lane sees which entry depends on the launch shape alone (blockIdx.x / gridDim.x: a second grid
 // dimension may carry something else).
 template <class F>
 OT_DEV void hit_list_for_each(int64_t n, const unsigned int* __restrict__ fill, F&& body) {
     if (!fill) {
-        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) body(i);
+        dense_for_each(n, body);
         return;
     }
     // work items = (piece, slice of OT_HIT_SLICE entries): a workgroup per whole piece left the 1024 pieces of a long list

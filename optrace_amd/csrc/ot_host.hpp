@@ -1,7 +1,7 @@
 // Host plumbing shared by the translation units of the C-ABI (ot_api.hip and ot_*_api.hip, one per stage): error reporting,
-// launch shapes, the scratch pool's front door, surface compilation and the source ranges.  Functions are declared here and
-// defined once, in the unit named beside them.  All of them are internal to the library: hidden visibility, so that the
-// dynamic symbol table holds the C-ABI and the kernels' host stubs.
+// launch shapes, the checks of a ray section, the scratch pool's front door, surface compilation and the source ranges.
+// Functions are declared here and defined once, in the unit named beside them.  All of them are internal to the library:
+// hidden visibility, so that the dynamic symbol table holds the C-ABI and the kernels' host stubs.
 #pragma once
 #include <stdint.h>
 
@@ -21,6 +21,8 @@ static inline void for_ray_chunks(int64_t first, int64_t count, F&& fn) {
 #ifndef OT_HOST_CHUNKS_ONLY
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -56,6 +58,38 @@ struct Carver {
 };
 
 OT_INTERNAL int cu_count();  // ot_api.hip
+
+// Workgroups (of 256: OT_RED_THREADS) of a fixed-order reduction over n entries (ot_block_reduce.hpp), `cap` at the most: numbers
+// that follow from n alone, not from the device's CU count, so that the order of the sums -- and with it their bits -- is the
+// same on every device
+static inline unsigned reduce_blocks(int64_t n, int64_t cap) {
+    return (unsigned)std::max<int64_t>(1, std::min((n + 255) / 256, cap));
+}
+
+// Launch shape of an LDS-privatised f64 histogram over n >= 1 entries (spectrum, radial bins of the spot, pupil map): 1024
+// threads, a workgroup per 1024 entries up to one per CU, and `lds_wanted` bytes of sums per workgroup if they fit into 64 KiB,
+// which keeps two workgroups of LDS per CU free for other work; lds = 0 otherwise, and the kernel adds to global memory.
+struct HistShape {
+    dim3 grid, block;
+    size_t lds;
+};
+static inline HistShape hist_shape(int64_t n, size_t lds_wanted) {
+    const int64_t blocks = std::min<int64_t>((n + 1023) / 1024, cu_count());
+    return {dim3((unsigned)blocks), dim3(1024), lds_wanted <= 64 * 1024 ? lds_wanted : 0};
+}
+
+// ---- a section of the ray storage and a sphere behind it (ot_wavefront_*, ot_psf_rays) ------------------------------------
+// -> what is wrong, to follow the entry point's name in its message, or nullptr.  need_index: the index plane is read; c, radius:
+// the sphere, c = nullptr where the entry point takes none.
+static inline const char* bad_section_sphere(const ot_rays* rays, int64_t first, int64_t count, int32_t section, bool need_index,
+                                             const double* c, double radius) {
+    if (!rays || !rays->p || !rays->w || (need_index && !rays->n)) return "null argument";
+    if (first < 0 || count < 0 || first + count > rays->N) return "ray range outside the storage";
+    if (section < 0 || section > rays->nt - 2) return "section out of range";
+    if (c && !(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) && std::isfinite(radius) && radius != 0.0))
+        return "focus or radius not finite, or radius zero";
+    return nullptr;
+}
 
 // ---- scratch pool (ot_api.hip, ot_scratch.hpp) ----------------------------------------------------------------------
 enum { OT_WS_RENDER = 0, OT_WS_FUSED = 1, OT_WS_FUSED_HITS = 2, OT_WS_AUTO = 3, OT_WS_DET = 4, OT_WS_COLOR = 5, OT_WS_SAMPLE = 6 };

@@ -1,7 +1,5 @@
 // C-ABI, Huygens point spread function: ray records from the storage and the wavefront planes, and their coherent sum over an
 // image plane (Raytracer.huygens_psf).
-#include <cmath>
-
 #include "ot_host.hpp"
 #include "ot_psf.hpp"
 
@@ -13,12 +11,9 @@ extern "C" int64_t ot_psf_workspace(int64_t n, int32_t n_px) {
 
 extern "C" int ot_psf_rays(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const double* focus, double radius,
                            const double* opl, const double* moments, double* rec, void* stream) {
-    if (!rays || !rays->p || !rays->w || !rays->n || !rays->wl || !focus || !opl || !moments || !rec)
-        return fail(OT_ERR_INVALID, "ot_psf_rays: null argument");
-    if (first < 0 || count < 0 || first + count > rays->N) return fail(OT_ERR_INVALID, "ot_psf_rays: ray range outside the storage");
-    if (section < 0 || section > rays->nt - 2) return fail(OT_ERR_INVALID, "ot_psf_rays: section out of range");
-    if (!std::isfinite(focus[0]) || !std::isfinite(focus[1]) || !std::isfinite(focus[2]) || !std::isfinite(radius) || radius == 0.0)
-        return fail(OT_ERR_INVALID, "ot_psf_rays: focus or radius not finite, or radius zero");
+    if ((rays && !rays->wl) || !focus || !opl || !moments || !rec) return fail(OT_ERR_INVALID, "ot_psf_rays: null argument");
+    if (const char* bad = bad_section_sphere(rays, first, count, section, true, focus, radius))
+        return fail(OT_ERR_INVALID, std::string("ot_psf_rays: ") + bad);
     if (count == 0) return OT_OK;
     if (int rc = require_device()) return rc;
     hipLaunchKernelGGL(psf_rays_kernel, grid_for(count), dim3(OT_PSF_THREADS), 0, (hipStream_t)stream, *rays, first, count, (int)section,

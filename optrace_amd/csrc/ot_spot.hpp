@@ -5,8 +5,8 @@
 //   pass 2  about the centroid c of pass 1, d = p - c formed before squaring: sum w dx^2, sum w dy^2, sum w dx dy, max r^2
 //   pass 3  sum w per radial bin min(floor(r / r_max * n_radii), n_radii - 1)
 //   pass 4  sum w exp(-2 pi i nu d) for K frequencies and both axes
-// Passes 1, 2 and 4 add in an order that the launch shape fixes -- lane accumulators over the walk, __shfl_down across the
-// wave, LDS across the four waves, one partial per workgroup, a last kernel over the partials -- so two calls return the
+// Passes 1, 2 and 4 add in the fixed order of ot_block_reduce.hpp -- lane accumulators over the walk, the workgroup's fold, one
+// partial per workgroup, a last kernel over the partials (reduce_final_kernel for the moments) -- so two calls return the
 // same bits.  Pass 3 adds with f64 atomics.  Every pass reads the results of those before it from device memory: nothing
 // comes back to the host in between.
 // Defines kernels that are no templates: included by ot_spot_api.hip alone.
@@ -20,9 +20,9 @@
 enum { SPOT_W = 0, SPOT_WX, SPOT_WY, SPOT_COUNT, SPOT_WDX2, SPOT_WDY2, SPOT_WDXDY, SPOT_R2MAX, SPOT_M };
 
 // part[gridDim.x][4]
-__global__ __launch_bounds__(OT_SPOT_THREADS) void spot_first_kernel(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
-                                                                     const float* __restrict__ w, const unsigned int* __restrict__ fill,
-                                                                     double* __restrict__ part) {
+__global__ __launch_bounds__(OT_RED_THREADS) void spot_first_kernel(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
+                                                                    const float* __restrict__ w, const unsigned int* __restrict__ fill,
+                                                                    double* __restrict__ part) {
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     hit_list_for_each(n, fill, [&](int64_t i) {
         const float wi = w[i];
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(OT_SPOT_THREADS) void spot_first_kernel(int64_t n, 
         v[2] += wd * y[i];
         v[3] += 1.0;  // (exact up to 2^53 hits)
     });
-    spot_block_reduce<4, -1>(v, part + 4 * (int64_t)blockIdx.x);
+    block_reduce_fixed<4, -1>(v, part + 4 * (int64_t)blockIdx.x);
 }
 
 // the centroid every later pass subtracts: the same two IEEE quotients as the host forms from the record
@@ -43,9 +43,9 @@ struct SpotCentre {
 OT_DEV SpotCentre spot_centre(const double* __restrict__ mom) { return {mom[SPOT_WX] / mom[SPOT_W], mom[SPOT_WY] / mom[SPOT_W]}; }
 
 // part[gridDim.x][4]
-__global__ __launch_bounds__(OT_SPOT_THREADS) void spot_central_kernel(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
-                                                                       const float* __restrict__ w, const unsigned int* __restrict__ fill,
-                                                                       const double* __restrict__ mom, double* __restrict__ part) {
+__global__ __launch_bounds__(OT_RED_THREADS) void spot_central_kernel(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
+                                                                      const float* __restrict__ w, const unsigned int* __restrict__ fill,
+                                                                      const double* __restrict__ mom, double* __restrict__ part) {
     const SpotCentre c = spot_centre(mom);
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     hit_list_for_each(n, fill, [&](int64_t i) {
@@ -57,26 +57,7 @@ __global__ __launch_bounds__(OT_SPOT_THREADS) void spot_central_kernel(int64_t n
         v[2] += wd * (dx * dy);
         v[3] = fmax(v[3], dx * dx + dy * dy);
     });
-    spot_block_reduce<4, 3>(v, part + 4 * (int64_t)blockIdx.x);
-}
-
-// part[nblocks][4] -> out[4]: wave m takes quantity m, lane l the partials l, l + 64, ... in that order, then the lanes
-// fold as in the workgroups.  One workgroup of four waves.
-__global__ __launch_bounds__(OT_SPOT_THREADS) void spot_moments_final_kernel(const double* __restrict__ part, int nblocks, int maxi,
-                                                                             double* __restrict__ out) {
-    const int m = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool is_max = m == maxi;
-    double r = 0.0;
-    for (int b = lane; b < nblocks; b += 64) {
-        const double p = part[4 * b + m];
-        r = is_max ? fmax(r, p) : r + p;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double other = __shfl_down(r, o);
-        r = is_max ? fmax(r, other) : r + other;
-    }
-    if (lane == 0) out[m] = r;
+    block_reduce_fixed<4, 3>(v, part + 4 * (int64_t)blockIdx.x);
 }
 
 // pass 3: hist[n_radii] += w.  LDS-privatised when the bins fit (lds_bins > 0), otherwise global atomics.
@@ -119,10 +100,10 @@ __global__ __launch_bounds__(1024) void spot_radial_kernel(int64_t n, const doub
 // pass 4: workgroup (bx, by) walks the list as workgroup bx of gridDim.x for the frequencies [8 by, 8 by + 8).
 // part[gridDim.x][gridDim.y][4][8]: re x | im x | re y | im y of the chunk.  The phase is kept in turns: t = nu d, t -= rint(t), so that
 // sincospi_small sees |2 t| <= 1 whatever nu and d are.  Four waves per SIMD (128 VGPRs): the accumulators take 64 of them.
-__global__ __launch_bounds__(OT_SPOT_THREADS, 4) void spot_otf_kernel(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
-                                                                   const float* __restrict__ w, const unsigned int* __restrict__ fill,
-                                                                   const double* __restrict__ mom, const double* __restrict__ freq, int K,
-                                                                   double* __restrict__ part) {
+__global__ __launch_bounds__(OT_RED_THREADS, 4) void spot_otf_kernel(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
+                                                                     const float* __restrict__ w, const unsigned int* __restrict__ fill,
+                                                                     const double* __restrict__ mom, const double* __restrict__ freq, int K,
+                                                                     double* __restrict__ part) {
     const SpotCentre c = spot_centre(mom);
     const int k0 = blockIdx.y * OT_SPOT_CHUNK;
     double nu[OT_SPOT_CHUNK];
@@ -148,12 +129,12 @@ __global__ __launch_bounds__(OT_SPOT_THREADS, 4) void spot_otf_kernel(int64_t n,
             v[3 * OT_SPOT_CHUNK + j] -= wd * sn;
         }
     });
-    spot_block_reduce<4 * OT_SPOT_CHUNK, -1>(v, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * (4 * OT_SPOT_CHUNK));
+    block_reduce_fixed<4 * OT_SPOT_CHUNK, -1>(v, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * (4 * OT_SPOT_CHUNK));
 }
 
 // part[nblocks][chunks][4][8] -> out[4][K]: thread (q, k) adds its partials in index order
-__global__ __launch_bounds__(OT_SPOT_THREADS) void spot_otf_final_kernel(const double* __restrict__ part, int nblocks, int K,
-                                                                         double* __restrict__ out) {
+__global__ __launch_bounds__(OT_RED_THREADS) void spot_otf_final_kernel(const double* __restrict__ part, int nblocks, int K,
+                                                                        double* __restrict__ out) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= 4 * K) return;
     const int q = j / K, k = j % K, chunks = (K + OT_SPOT_CHUNK - 1) / OT_SPOT_CHUNK;

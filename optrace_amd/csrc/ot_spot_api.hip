@@ -2,25 +2,17 @@
 #include "ot_host.hpp"
 #include "ot_spot.hpp"
 
-// workgroups of the streaming passes (1, 2) and, times the frequency chunks, of pass 4: fixed numbers, not the device's CU
-// count, so that the order of the sums -- and with it their bits -- is the same on every device
-static unsigned spot_blocks(int64_t n, int64_t cap) {
-    int64_t blocks = (n + OT_SPOT_THREADS - 1) / OT_SPOT_THREADS;
-    if (blocks > cap) blocks = cap;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
 extern "C" int ot_spot_moments(int64_t n, const uint32_t* fill, const double* x, const double* y, const float* w, double* workspace,
                                double* moments, void* stream) {
     if (n < 0 || !x || !y || !w || !workspace || !moments) return fail(OT_ERR_INVALID, "ot_spot_moments: null argument");
     if (n == 0) return OT_OK;
     if (int rc = require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const unsigned blocks = spot_blocks(n, OT_SPOT_BLOCKS);
-    hipLaunchKernelGGL(spot_first_kernel, dim3(blocks), dim3(OT_SPOT_THREADS), 0, st, n, x, y, w, fill, workspace);
-    hipLaunchKernelGGL(spot_moments_final_kernel, dim3(1), dim3(OT_SPOT_THREADS), 0, st, workspace, (int)blocks, -1, moments);
-    hipLaunchKernelGGL(spot_central_kernel, dim3(blocks), dim3(OT_SPOT_THREADS), 0, st, n, x, y, w, fill, moments, workspace);
-    hipLaunchKernelGGL(spot_moments_final_kernel, dim3(1), dim3(OT_SPOT_THREADS), 0, st, workspace, (int)blocks, 3, moments + 4);
+    const unsigned blocks = reduce_blocks(n, OT_SPOT_BLOCKS);
+    hipLaunchKernelGGL(spot_first_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, x, y, w, fill, workspace);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 4, 0u, 0u, moments);
+    hipLaunchKernelGGL(spot_central_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, x, y, w, fill, moments, workspace);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 4, 1u << 3, 0u, moments + 4);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }
@@ -32,14 +24,9 @@ extern "C" int ot_spot_radial(int64_t n, const uint32_t* fill, const double* x, 
     if (n_radii > OT_SPOT_MAX_RADII) return fail(OT_ERR_UNSUPPORTED, "ot_spot_radial: more than 65536 radial bins");
     if (n == 0) return OT_OK;
     if (int rc = require_device()) return rc;
-    // the LDS budget of the spectrum histogram: 64 KiB keeps two workgroups of LDS per CU free for other work
-    const size_t lds = (size_t)n_radii * sizeof(double);
-    const int lds_bins = lds <= 64 * 1024 ? n_radii : 0;
-    int64_t blocks = (n + 1023) / 1024;
-    const int64_t cap = cu_count();
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(spot_radial_kernel, dim3((unsigned)blocks), dim3(1024), lds_bins ? lds : 0, (hipStream_t)stream, n, x, y, w, fill,
-                       moments, n_radii, lds_bins, hist);
+    const HistShape hs = hist_shape(n, (size_t)n_radii * sizeof(double));
+    hipLaunchKernelGGL(spot_radial_kernel, hs.grid, hs.block, hs.lds, (hipStream_t)stream, n, x, y, w, fill, moments, n_radii,
+                       hs.lds ? n_radii : 0, hist);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }
@@ -55,9 +42,9 @@ extern "C" int ot_spot_otf(int64_t n, const uint32_t* fill, const double* x, con
     // about OT_SPOT_BLOCKS workgroups in all, at least 64 walkers per chunk: OT_SPOT_WS(K) holds their partials
     const int chunks = (K + OT_SPOT_CHUNK - 1) / OT_SPOT_CHUNK;
     const int per_chunk = OT_SPOT_BLOCKS / chunks;
-    const unsigned bx = spot_blocks(n, per_chunk < 64 ? 64 : per_chunk);
-    hipLaunchKernelGGL(spot_otf_kernel, dim3(bx, (unsigned)chunks), dim3(OT_SPOT_THREADS), 0, st, n, x, y, w, fill, moments, freq, K, workspace);
-    hipLaunchKernelGGL(spot_otf_final_kernel, grid_for(4 * (int64_t)K), dim3(OT_SPOT_THREADS), 0, st, workspace, (int)bx, K, otf);
+    const unsigned bx = reduce_blocks(n, per_chunk < 64 ? 64 : per_chunk);
+    hipLaunchKernelGGL(spot_otf_kernel, dim3(bx, (unsigned)chunks), dim3(OT_RED_THREADS), 0, st, n, x, y, w, fill, moments, freq, K, workspace);
+    hipLaunchKernelGGL(spot_otf_final_kernel, grid_for(4 * (int64_t)K), dim3(OT_RED_THREADS), 0, st, workspace, (int)bx, K, otf);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }

@@ -6,49 +6,26 @@
 //   moments  two passes over those planes: sums, then central sums about the means of the first
 //   map      sum w and sum w OPD per cell of an n_grid x n_grid pupil grid (f64 atomics)
 //   zernike  G = sum w Z Z^T (upper triangle) and g = sum w Z OPD for the Noll polynomials Z_1 .. Z_J
-// focus, moments and zernike add in the fixed order of ot_block_reduce.hpp and a last kernel over the workgroups' partials: two
-// calls return the same bits.  Every pass reads the results of those before it from device memory.
+// focus, moments and zernike add in the fixed order of ot_block_reduce.hpp and a last kernel over the workgroups' partials
+// (its reduce_final_kernel; wf_zernike_final_kernel): two calls return the same bits.  Every pass reads the results of those
+// before it from device memory.
 // Defines kernels that are no templates: included by ot_wavefront_api.hip alone.
 #pragma once
 #include "ot_block_reduce.hpp"
 #include "ot_device.hpp"
+#include "ot_hit_list.hpp"       // dense_for_each: the walk of the planes
 #include "ot_wavefront_ray.hpp"  // the rays of a section, their sphere step, the slots of the records
 
-#define OT_WF_THREADS OT_SPOT_THREADS
-
-// part[nblocks][M] -> out[M]: wave wv takes the quantities wv, wv + 4, ..., lane l the partials l, l + 64, ... in that order,
-// then the lanes fold as in the workgroups.  Bit m of maxmask: quantity m is a maximum; of negmask: it is stored negated (a
-// minimum carried as the maximum of the negated values).  One workgroup of four waves.
-__global__ __launch_bounds__(OT_WF_THREADS) void wf_final_kernel(const double* __restrict__ part, int nblocks, int M, unsigned maxmask,
-                                                                 unsigned negmask, double* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    for (int m = threadIdx.x >> 6; m < M; m += OT_SPOT_WAVES) {  // (wave-uniform)
-        const bool is_max = (maxmask >> m) & 1u;
-        double r = is_max ? -__builtin_inf() : 0.0;
-        for (int b = lane; b < nblocks; b += 64) {
-            const double p = part[(int64_t)M * b + m];
-            r = is_max ? fmax(r, p) : r + p;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double other = __shfl_down(r, o);
-            r = is_max ? fmax(r, other) : r + other;
-        }
-        if (lane == 0) out[m] = ((negmask >> m) & 1u) ? -r : r;
-    }
-}
-
 // part[gridDim.x][17]: W | count | sum w (p - origin) | sum w s | sum w (I - s s^T): xx xy xz yy yz zz | sum w (I - s s^T) (p - origin)
-__global__ __launch_bounds__(OT_WF_THREADS) void wf_focus_kernel(ot_rays R, int64_t first, int64_t count, int k, double ox, double oy,
-                                                                 double oz, double* __restrict__ part) {
+__global__ __launch_bounds__(OT_RED_THREADS) void wf_focus_kernel(ot_rays R, int64_t first, int64_t count, int k, double ox, double oy,
+                                                                  double oz, double* __restrict__ part) {
     double v[WFF_M];
 #pragma unroll
     for (int m = 0; m < WFF_M; m++) v[m] = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    dense_for_each(count, [&](int64_t i) {
         const int64_t r = first + i;
         const WfRay q = wf_section(R, r, k, wf_position(R, r, k));
-        if (!q.used) continue;
+        if (!q.used) return;
         const double w = q.w, px = q.p.x - ox, py = q.p.y - oy, pz = q.p.z - oz;
         const V3 s = q.s;
         const double sp = s.x * px + s.y * py + s.z * pz;
@@ -69,17 +46,17 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_focus_kernel(ot_rays R, int6
         v[WFF_B + 0] += w * (px - s.x * sp);
         v[WFF_B + 1] += w * (py - s.y * sp);
         v[WFF_B + 2] += w * (pz - s.z * sp);
-    }
-    spot_block_reduce<WFF_M, -1>(v, part + WFF_M * (int64_t)blockIdx.x);
+    });
+    block_reduce_fixed<WFF_M, -1>(v, part + WFF_M * (int64_t)blockIdx.x);
 }
 
 // The hot pass, one thread per ray of [first, first + count): (k + 2) positions and (k + 1) indices read plane by plane
 // (coalesced: neighbouring lanes, neighbouring rays), four dense planes written.  Rays that are not used leave NaN in u, v and
 // opl and 0 in w_out; those whose line misses the sphere are counted in `missed` besides.
-__global__ __launch_bounds__(OT_WF_THREADS) void wf_paths_kernel(ot_rays R, int64_t first, int64_t count, int k, double cx, double cy,
-                                                                 double cz, double radius, double* __restrict__ u, double* __restrict__ v,
-                                                                 double* __restrict__ opl, float* __restrict__ w_out,
-                                                                 unsigned long long* __restrict__ missed) {
+__global__ __launch_bounds__(OT_RED_THREADS) void wf_paths_kernel(ot_rays R, int64_t first, int64_t count, int k, double cx, double cy,
+                                                                  double cz, double radius, double* __restrict__ u, double* __restrict__ v,
+                                                                  double* __restrict__ opl, float* __restrict__ w_out,
+                                                                  unsigned long long* __restrict__ missed) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool miss = false;
     if (i < count) {
@@ -117,15 +94,14 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_paths_kernel(ot_rays R, int6
 
 // ---- moments of the planes -------------------------------------------------------------------------------------------
 // part[gridDim.x][8]: the first eight slots of the record, the minimum as the maximum of -opl
-__global__ __launch_bounds__(OT_WF_THREADS) void wf_first_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
-                                                                 const double* __restrict__ opl, const float* __restrict__ w,
-                                                                 const float* __restrict__ wl, double* __restrict__ part) {
+__global__ __launch_bounds__(OT_RED_THREADS) void wf_first_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
+                                                                  const double* __restrict__ opl, const float* __restrict__ w,
+                                                                  const float* __restrict__ wl, double* __restrict__ part) {
     const double inf = __builtin_inf();
     double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -inf, -inf};
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    dense_for_each(n, [&](int64_t i) {
         const float wi = w[i];
-        if (!(wi > 0.f)) continue;
+        if (!(wi > 0.f)) return;
         const double wd = (double)wi, l = opl[i];
         a[WF_W] += wd;
         a[WF_COUNT] += 1.0;
@@ -135,25 +111,24 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_first_kernel(int64_t n, cons
         if (wl) a[WF_WWL] += wd * (double)wl[i];
         a[WF_OPL_MIN] = fmax(a[WF_OPL_MIN], -l);
         a[WF_OPL_MAX] = fmax(a[WF_OPL_MAX], l);
-    }
-    spot_block_reduce<8, WF_OPL_MIN, WF_OPL_MAX>(a, part + 8 * (int64_t)blockIdx.x);
+    });
+    block_reduce_fixed<8, WF_OPL_MIN, WF_OPL_MAX>(a, part + 8 * (int64_t)blockIdx.x);
 }
 
 // part[gridDim.x][2]: sum w opd^2 | max (du^2 + dv^2)
-__global__ __launch_bounds__(OT_WF_THREADS) void wf_central_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
-                                                                   const double* __restrict__ opl, const float* __restrict__ w,
-                                                                   const double* __restrict__ mom, double* __restrict__ part) {
+__global__ __launch_bounds__(OT_RED_THREADS) void wf_central_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
+                                                                    const double* __restrict__ opl, const float* __restrict__ w,
+                                                                    const double* __restrict__ mom, double* __restrict__ part) {
     const WfMeans c = wf_means(mom);
     double a[2] = {0.0, 0.0};
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    dense_for_each(n, [&](int64_t i) {
         const float wi = w[i];
-        if (!(wi > 0.f)) continue;
+        if (!(wi > 0.f)) return;
         const double d = opl[i] - c.opl, du = u[i] - c.u, dv = v[i] - c.v;
         a[0] += (double)wi * (d * d);
         a[1] = fmax(a[1], du * du + dv * dv);
-    }
-    spot_block_reduce<2, 1>(a, part + 2 * (int64_t)blockIdx.x);
+    });
+    block_reduce_fixed<2, 1>(a, part + 2 * (int64_t)blockIdx.x);
 }
 
 // The pupil radius the later passes divide by when the caller gives none, stored so that the host reports this very number
@@ -191,6 +166,7 @@ __global__ __launch_bounds__(1024) void wf_map_kernel(int64_t n, const double* _
     const WfPupil P = wf_pupil(mom, pupil_radius);
     const double mean = wf_means(mom).opl, fn = (double)n_grid;
     const int64_t cells = (int64_t)n_grid * n_grid;
+    // (dense_for_each written out: through it the selects of the cell index compile to branches; profiles/analysis_core)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float wi = w[i];
@@ -289,10 +265,10 @@ OT_DEV void wf_zernike_all(double x, double y, double (&Z)[JT]) {
 // (a = b in the middle chunk of an odd JT: its slots s < c, JT and JT + 2 repeat others of the chunk and are dropped).  Every Z index but
 // a and b is a compile-time one, so Z and the accumulators stay in registers.  part[gridDim.x][gridDim.y][JT + 3].
 template <int JT>
-__global__ __launch_bounds__(OT_WF_THREADS) void wf_zernike_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
-                                                                   const double* __restrict__ opl, const float* __restrict__ w,
-                                                                   const double* __restrict__ mom, double pupil_radius,
-                                                                   double* __restrict__ part) {
+__global__ __launch_bounds__(OT_RED_THREADS) void wf_zernike_kernel(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
+                                                                    const double* __restrict__ opl, const float* __restrict__ w,
+                                                                    const double* __restrict__ mom, double pupil_radius,
+                                                                    double* __restrict__ part) {
     constexpr int S = JT + 3;
     const WfPupil P = wf_pupil(mom, pupil_radius);
     const double mean = wf_means(mom).opl;
@@ -300,6 +276,7 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_zernike_kernel(int64_t n, co
     double acc[S];
 #pragma unroll
     for (int s = 0; s < S; s++) acc[s] = 0.0;
+    // (dense_for_each written out: through it the JT = 15 kernel's scalar-register spills move by two; profiles/analysis_core)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float wi = w[i];
@@ -322,13 +299,13 @@ __global__ __launch_bounds__(OT_WF_THREADS) void wf_zernike_kernel(int64_t n, co
         acc[JT + 1] += wa * opd;
         acc[JT + 2] += wb * opd;
     }
-    spot_block_reduce<S, -1>(acc, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * S);
+    block_reduce_fixed<S, -1>(acc, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * S);
 }
 
 // part[nblocks][chunks][JT + 3] -> out: G's upper triangle row by row (i <= j < J), then g[J].  One thread per slot of a chunk
 // adds its partials in index order and stores the sum where its (i, j) belongs, if that lies within J.
-__global__ __launch_bounds__(OT_WF_THREADS) void wf_zernike_final_kernel(const double* __restrict__ part, int nblocks, int JT, int J,
-                                                                         double* __restrict__ out) {
+__global__ __launch_bounds__(OT_RED_THREADS) void wf_zernike_final_kernel(const double* __restrict__ part, int nblocks, int JT, int J,
+                                                                          double* __restrict__ out) {
     const int S = JT + 3, chunks = (JT + 1) / 2;
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= chunks * S) return;

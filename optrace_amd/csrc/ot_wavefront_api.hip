@@ -1,38 +1,22 @@
 // C-ABI, wavefront analysis: optical path to a reference sphere, its moments, pupil map and Zernike normal equations
 // (Raytracer.wavefront_analysis).
-#include <cmath>
-
 #include "ot_host.hpp"
 #include "ot_wavefront.hpp"
-
-// workgroups of the streaming reductions: fixed numbers, not the device's CU count, so that the order of the sums -- and with
-// it their bits -- is the same on every device
-static unsigned wf_blocks(int64_t n, int64_t cap) {
-    int64_t blocks = (n + OT_WF_THREADS - 1) / OT_WF_THREADS;
-    if (blocks > cap) blocks = cap;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
-static const char* wf_bad_rays(const ot_rays* rays, int64_t first, int64_t count, int32_t section, bool need_index) {
-    if (!rays || !rays->p || !rays->w || (need_index && !rays->n)) return "null argument";
-    if (first < 0 || count < 0 || first + count > rays->N) return "ray range outside the storage";
-    if (section < 0 || section > rays->nt - 2) return "section out of range";
-    return nullptr;
-}
 
 extern "C" int ot_wavefront_focus(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const double* origin,
                                   double* workspace, double* sums, void* stream) {
     if (!origin || !workspace || !sums) return fail(OT_ERR_INVALID, "ot_wavefront_focus: null argument");
-    if (const char* bad = wf_bad_rays(rays, first, count, section, false)) return fail(OT_ERR_INVALID, std::string("ot_wavefront_focus: ") + bad);
+    if (const char* bad = bad_section_sphere(rays, first, count, section, false, nullptr, 0.0))
+        return fail(OT_ERR_INVALID, std::string("ot_wavefront_focus: ") + bad);
     if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
         return fail(OT_ERR_INVALID, "ot_wavefront_focus: origin not finite");
     if (count == 0) return OT_OK;
     if (int rc = require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const unsigned blocks = wf_blocks(count, OT_WF_BLOCKS);
-    hipLaunchKernelGGL(wf_focus_kernel, dim3(blocks), dim3(OT_WF_THREADS), 0, st, *rays, first, count, (int)section, origin[0], origin[1],
+    const unsigned blocks = reduce_blocks(count, OT_WF_BLOCKS);
+    hipLaunchKernelGGL(wf_focus_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, *rays, first, count, (int)section, origin[0], origin[1],
                        origin[2], workspace);
-    hipLaunchKernelGGL(wf_final_kernel, dim3(1), dim3(OT_WF_THREADS), 0, st, workspace, (int)blocks, (int)WFF_M, 0u, 0u, sums);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, (int)WFF_M, 0u, 0u, sums);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }
@@ -40,14 +24,13 @@ extern "C" int ot_wavefront_focus(const ot_rays* rays, int64_t first, int64_t co
 extern "C" int ot_wavefront_paths(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const double* focus, double radius,
                                   double* u, double* v, double* opl, float* w_out, int64_t* missed, void* stream) {
     if (!focus || !u || !v || !opl || !w_out || !missed) return fail(OT_ERR_INVALID, "ot_wavefront_paths: null argument");
-    if (const char* bad = wf_bad_rays(rays, first, count, section, true)) return fail(OT_ERR_INVALID, std::string("ot_wavefront_paths: ") + bad);
-    if (!std::isfinite(focus[0]) || !std::isfinite(focus[1]) || !std::isfinite(focus[2]) || !std::isfinite(radius) || radius == 0.0)
-        return fail(OT_ERR_INVALID, "ot_wavefront_paths: focus or radius not finite, or radius zero");
+    if (const char* bad = bad_section_sphere(rays, first, count, section, true, focus, radius))
+        return fail(OT_ERR_INVALID, std::string("ot_wavefront_paths: ") + bad);
     if (count == 0) return OT_OK;
     if (int rc = require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(missed, 0, sizeof(int64_t), st));
-    hipLaunchKernelGGL(wf_paths_kernel, grid_for(count), dim3(OT_WF_THREADS), 0, st, *rays, first, count, (int)section, focus[0], focus[1],
+    hipLaunchKernelGGL(wf_paths_kernel, grid_for(count), dim3(OT_RED_THREADS), 0, st, *rays, first, count, (int)section, focus[0], focus[1],
                        focus[2], radius, u, v, opl, w_out, (unsigned long long*)missed);
     HIP_TRY(hipGetLastError());
     return OT_OK;
@@ -59,12 +42,12 @@ extern "C" int ot_wavefront_moments(int64_t n, const double* u, const double* v,
     if (n == 0) return OT_OK;
     if (int rc = require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const unsigned blocks = wf_blocks(n, OT_WF_BLOCKS);
+    const unsigned blocks = reduce_blocks(n, OT_WF_BLOCKS);
     const unsigned maxima = (1u << WF_OPL_MIN) | (1u << WF_OPL_MAX);
-    hipLaunchKernelGGL(wf_first_kernel, dim3(blocks), dim3(OT_WF_THREADS), 0, st, n, u, v, opl, w, wl, workspace);
-    hipLaunchKernelGGL(wf_final_kernel, dim3(1), dim3(OT_WF_THREADS), 0, st, workspace, (int)blocks, 8, maxima, 1u << WF_OPL_MIN, moments);
-    hipLaunchKernelGGL(wf_central_kernel, dim3(blocks), dim3(OT_WF_THREADS), 0, st, n, u, v, opl, w, moments, workspace);
-    hipLaunchKernelGGL(wf_final_kernel, dim3(1), dim3(OT_WF_THREADS), 0, st, workspace, (int)blocks, 2, 2u, 0u, moments + WF_WOPD2);
+    hipLaunchKernelGGL(wf_first_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, u, v, opl, w, wl, workspace);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 8, maxima, 1u << WF_OPL_MIN, moments);
+    hipLaunchKernelGGL(wf_central_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, u, v, opl, w, moments, workspace);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 2, 2u, 0u, moments + WF_WOPD2);
     hipLaunchKernelGGL(wf_pupil_radius_kernel, dim3(1), dim3(1), 0, st, moments);
     HIP_TRY(hipGetLastError());
     return OT_OK;
@@ -81,14 +64,10 @@ extern "C" int ot_wavefront_map(int64_t n, const double* u, const double* v, con
     if (wf_bad_pupil(pupil_radius)) return fail(OT_ERR_INVALID, "ot_wavefront_map: pupil radius neither NaN nor above zero");
     if (n == 0) return OT_OK;
     if (int rc = require_device()) return rc;
-    // the LDS budget of the spot histogram: 64 KiB keeps two workgroups of LDS per CU free for other work
-    const size_t lds = 2 * (size_t)n_grid * n_grid * sizeof(double);
-    const int lds_cells = lds <= 64 * 1024 ? 2 * n_grid * n_grid : 0;
-    int64_t blocks = (n + 1023) / 1024;
-    const int64_t cap = cu_count();
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(wf_map_kernel, dim3((unsigned)blocks), dim3(1024), lds_cells ? lds : 0, (hipStream_t)stream, n, u, v, opl, w, moments,
-                       pupil_radius, (int)n_grid, lds_cells, map);
+    const int cells2 = 2 * n_grid * n_grid;
+    const HistShape hs = hist_shape(n, (size_t)cells2 * sizeof(double));
+    hipLaunchKernelGGL(wf_map_kernel, hs.grid, hs.block, hs.lds, (hipStream_t)stream, n, u, v, opl, w, moments, pupil_radius, (int)n_grid,
+                       hs.lds ? cells2 : 0, map);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }
@@ -99,10 +78,10 @@ static void wf_zernike_launch(int64_t n, const double* u, const double* v, const
     // about OT_WF_BLOCKS workgroups in all, at least 64 walkers per chunk: OT_WF_WS holds their partials
     constexpr int chunks = (JT + 1) / 2, per_chunk = OT_WF_BLOCKS / chunks;
     static_assert((int64_t)(per_chunk < 64 ? 64 : per_chunk) * chunks * (JT + 3) <= OT_WF_WS, "workspace");
-    const unsigned bx = wf_blocks(n, per_chunk < 64 ? 64 : per_chunk);
-    hipLaunchKernelGGL(wf_zernike_kernel<JT>, dim3(bx, (unsigned)chunks), dim3(OT_WF_THREADS), 0, st, n, u, v, opl, w, moments, pupil_radius,
+    const unsigned bx = reduce_blocks(n, per_chunk < 64 ? 64 : per_chunk);
+    hipLaunchKernelGGL(wf_zernike_kernel<JT>, dim3(bx, (unsigned)chunks), dim3(OT_RED_THREADS), 0, st, n, u, v, opl, w, moments, pupil_radius,
                        workspace);
-    hipLaunchKernelGGL(wf_zernike_final_kernel, grid_for(chunks * (JT + 3)), dim3(OT_WF_THREADS), 0, st, workspace, (int)bx, JT, J, out);
+    hipLaunchKernelGGL(wf_zernike_final_kernel, grid_for(chunks * (JT + 3)), dim3(OT_RED_THREADS), 0, st, workspace, (int)bx, JT, J, out);
 }
 
 extern "C" int ot_wavefront_zernike(int64_t n, const double* u, const double* v, const double* opl, const float* w, const double* moments,

@@ -28,7 +28,7 @@ def check_arguments(nt: int, section, focus, radius, n_px, size, dz):
     if size is not None:
         size = _wavefront._finite_number("size", size, positive=True)
     dz = _wavefront._finite_number("dz", dz)
-    focus, radius, _ = _wavefront.check_arguments(nt, section, focus, radius, 1, 1, None)
+    focus, radius = _wavefront.check_sphere_arguments(nt, section, focus, radius)
     return focus, radius, size, dz
 
 
@@ -100,59 +100,38 @@ def analyse(rays, first: int, count: int, section: int, origin, focus, radius, n
     returned them.  The host reads the focus sums (where focus or radius is left to it), the moments record (where size is) and,
     at the end, one buffer with everything else."""
     import torch
-    from ._device import require_device, ptr, stream_ptr
+    from ._device import ptr, stream_ptr
     lib = _capi.load_library()
-    dev = require_device()
-    if count < 1:
+    parts = [2 * n_px * n_px, 4, 2]  # field | centre | wl range
+    S = _wavefront.sphere_stage(rays, first, count, section, origin, focus, radius, sum(parts))
+    focus, radius = S.focus, S.radius
+    if S.empty:
         return _empty(section, focus, radius, n_px, size, dz, **kwargs)
     st = stream_ptr()
-    R = rays._rays_struct()
-    ws = torch.empty(_capi.WF_WS, dtype=torch.float64, device=dev)
-    d3 = C.c_double * 3
-    if focus is None or radius is None:
-        sums = torch.zeros(_capi.WF_FOCUS_M, dtype=torch.float64, device=dev)
-        origin = np.array(origin, dtype=np.float64)
-        _capi.check(lib.ot_wavefront_focus(C.byref(R), first, count, section, d3(*origin), ptr(ws), ptr(sums), st))
-        f = sums.cpu().numpy()
-        if not f[0] > 0:
-            return _empty(section, focus, radius, n_px, size, dz, **kwargs)
-        focus, radius = _wavefront.reference_sphere(f, origin, focus, radius)
-
-    rays._dev["n"]  # (the index plane is written when it is read: this fills it if the trace left it stale)
-    planes = torch.empty(3 * count, dtype=torch.float64, device=dev)
-    u, v, opl = planes[:count], planes[count:2 * count], planes[2 * count:]
-    w = torch.empty(count, dtype=torch.float32, device=dev)
-    M, cells = _capi.WF_M, n_px * n_px
-    res = torch.zeros(M + 2 * cells + 4 + 3, dtype=torch.float64, device=dev)  # moments | field | centre | wl range | missed
-    mom, field, centre, wl_range = res[:M], res[M:M + 2 * cells], res[M + 2 * cells:M + 2 * cells + 4], res[-3:-1]
-    missed = res[-1:].view(torch.int64)
-    _capi.check(lib.ot_wavefront_paths(C.byref(R), first, count, section, d3(*focus), radius, ptr(u), ptr(v), ptr(opl), ptr(w),
-                                       ptr(missed), st))
-    wl = rays._dev["wl"][first:first + count]
-    _capi.check(lib.ot_wavefront_moments(count, ptr(u), ptr(v), ptr(opl), ptr(w), ptr(wl), ptr(ws), ptr(mom), st))
+    field, centre, wl_range = S.extra.split(parts)
     # (for the warning alone: the range of the used rays' wavelengths)
-    used = w > 0
-    wl_range[0] = torch.where(used, wl, torch.inf).amin()
-    wl_range[1] = torch.where(used, wl, -torch.inf).amax()
+    used = S.w > 0
+    wl_range[0] = torch.where(used, S.wl, torch.inf).amin()
+    wl_range[1] = torch.where(used, S.wl, -torch.inf).amax()
     if size is None:
-        m = mom.cpu().numpy()
+        m = S.mom.cpu().numpy()
         if not m[0] > 0:
-            return _empty(section, focus, radius, n_px, size, dz, int(missed.cpu()[0]), **kwargs)
+            return _empty(section, focus, radius, n_px, size, dz, int(S.missed.cpu()[0]), **kwargs)
         size = default_size(m)
         if not (np.isfinite(size) and size > 0):
             raise RuntimeError("The used rays meet the reference sphere in one place, which gives the image no scale: pass `size`.")
-    rec = torch.empty(_capi.PSF_REC * count, dtype=torch.float64, device=dev)
-    _capi.check(lib.ot_psf_rays(C.byref(R), first, count, section, d3(*focus), radius, ptr(opl), ptr(mom), ptr(rec), st))
-    psf_ws = torch.empty(_capi.psf_ws(count, n_px), dtype=torch.float64, device=dev)
+    rec = torch.empty(_capi.PSF_REC * count, dtype=torch.float64, device=S.w.device)
+    _capi.check(lib.ot_psf_rays(C.byref(S.R), first, count, section, (C.c_double * 3)(*focus), radius, ptr(S.opl), ptr(S.mom),
+                                ptr(rec), st))
+    psf_ws = torch.empty(_capi.psf_ws(count, n_px), dtype=torch.float64, device=S.w.device)
     _capi.check(lib.ot_psf_sum(count, ptr(rec), radius, n_px, size, dz, ptr(psf_ws), ptr(field), ptr(centre), st))
-    h = res.cpu().numpy()
-    n_missed = int(h[-1:].view(np.int64)[0])
-    m = h[:M]
+    m, n_missed, h = S.read()
     W = m[0]
     if not W > 0:
         return _empty(section, focus, radius, n_px, size, dz, n_missed, **kwargs)
-    if h[-3] != h[-2]:
-        warning(f"The used rays carry wavelengths from {h[-3]:.6g} nm to {h[-2]:.6g} nm and are added coherently, each with its own: "
-                "the point spread function is meaningful for a monochromatic source only.")
-    intensity, strehl, noise_floor = figures(h[M:M + 2 * cells].reshape(2, n_px, n_px), h[M + 2 * cells:M + 2 * cells + 4])
+    field, centre, wl_range = np.split(h, np.cumsum(parts)[:-1])
+    if wl_range[0] != wl_range[1]:
+        warning(f"The used rays carry wavelengths from {wl_range[0]:.6g} nm to {wl_range[1]:.6g} nm and are added coherently, each "
+                "with its own: the point spread function is meaningful for a monochromatic source only.")
+    intensity, strehl, noise_floor = figures(field.reshape(2, n_px, n_px), centre)
     return HuygensPSF(int(m[1]), W, n_missed, section, focus, radius, m[5] / W, size, dz, intensity, strehl, noise_floor, **kwargs)

@@ -57,15 +57,8 @@ def _finite_number(key: str, val, nonzero: bool = False, positive: bool = False)
     return float(val)
 
 
-def check_arguments(nt: int, section, focus, radius, n_zernike, n_grid, pupil_radius):
-    """Argument checks of `Raytracer.wavefront_analysis`, host only; nt: sections per ray of the geometry.
-    -> (focus as a float64 array or None, radius, pupil_radius as floats or None)."""
-    check_type("n_zernike", n_zernike, int)
-    check_not_below("n_zernike", n_zernike, 1)
-    check_not_above("n_zernike", n_zernike, _capi.WF_MAX_J)
-    check_type("n_grid", n_grid, int)
-    check_not_below("n_grid", n_grid, 1)
-    check_not_above("n_grid", n_grid, _capi.WF_MAX_GRID)
+def check_sphere_arguments(nt: int, section, focus, radius):
+    """The share of `check_arguments` that `psf.check_arguments` needs too.  -> (focus, radius), as there."""
     if section is not None:
         check_type("section", section, int)
         check_not_below("section", section, 0)
@@ -82,6 +75,19 @@ def check_arguments(nt: int, section, focus, radius, n_zernike, n_grid, pupil_ra
             raise ValueError("Property 'focus' needs to hold finite values only.")
     if radius is not None:
         radius = _finite_number("radius", radius, nonzero=True)
+    return focus, radius
+
+
+def check_arguments(nt: int, section, focus, radius, n_zernike, n_grid, pupil_radius):
+    """Argument checks of `Raytracer.wavefront_analysis`, host only; nt: sections per ray of the geometry.
+    -> (focus as a float64 array or None, radius, pupil_radius as floats or None)."""
+    check_type("n_zernike", n_zernike, int)
+    check_not_below("n_zernike", n_zernike, 1)
+    check_not_above("n_zernike", n_zernike, _capi.WF_MAX_J)
+    check_type("n_grid", n_grid, int)
+    check_not_below("n_grid", n_grid, 1)
+    check_not_above("n_grid", n_grid, _capi.WF_MAX_GRID)
+    focus, radius = check_sphere_arguments(nt, section, focus, radius)
     if pupil_radius is not None:
         pupil_radius = _finite_number("pupil_radius", pupil_radius, positive=True)
     return focus, radius, pupil_radius
@@ -180,21 +186,34 @@ def unpack_normal_equations(packed, J: int):
     return G + np.triu(G, 1).T, np.array(packed[tri:tri + J])
 
 
-def analyse(rays, first: int, count: int, section: int, origin, focus, radius, n_zernike: int, n_grid: int, pupil_radius,
-            **kwargs) -> WavefrontAnalysis:
-    """Figures of the rays [first, first + count) of the storage `rays` behind section `section`.  origin: a point near the
-    section's start that the device subtracts before it sums positions; the other arguments as `check_arguments` returned
-    them."""
+class SphereStage:
+    """What `sphere_stage` leaves.  focus, radius: the sphere, as given or as found; empty: no usable ray at the focus stage, and
+    nothing else set.  On the device: the planes u, v, opl, w of `ot_wavefront_paths`, wl of the storage, the views mom | missed
+    (int64) | extra of one zero-filled float64 buffer, the reductions' workspace ws; R: the rays struct of the C-ABI."""
+
+    def __init__(self, focus, radius) -> None:
+        self.focus, self.radius, self.empty = focus, radius, True
+
+    def read(self):
+        """-> (moments record, n_missed, extra) on the host: the whole buffer in one read."""
+        m, missed, extra = np.split(self._res.cpu().numpy(), [_capi.WF_M, _capi.WF_M + 1])
+        return m, int(missed.view(np.int64)[0]), extra
+
+
+def sphere_stage(rays, first: int, count: int, section: int, origin, focus, radius, extra: int) -> SphereStage:
+    """The start that wavefront analysis and Huygens PSF share, arguments as for `analyse`: the reference sphere (`ot_wavefront_focus`,
+    where focus or radius is left to it), the paths to it and their moments.  extra: doubles of the result buffer behind the
+    moments and the missed count, for the caller's own passes."""
     import torch
     from ._device import require_device, ptr, stream_ptr
     lib = _capi.load_library()
     dev = require_device()
-    J = n_zernike
+    S = SphereStage(focus, radius)
     if count < 1:
-        return _empty(section, focus, radius, J, n_grid, **kwargs)
+        return S
     st = stream_ptr()
-    R = rays._rays_struct()
-    ws = torch.empty(_capi.WF_WS, dtype=torch.float64, device=dev)
+    S.R = R = rays._rays_struct()
+    S.ws = ws = torch.empty(_capi.WF_WS, dtype=torch.float64, device=dev)
     d3 = C.c_double * 3
     if focus is None or radius is None:
         sums = torch.zeros(_capi.WF_FOCUS_M, dtype=torch.float64, device=dev)
@@ -202,27 +221,44 @@ def analyse(rays, first: int, count: int, section: int, origin, focus, radius, n
         _capi.check(lib.ot_wavefront_focus(C.byref(R), first, count, section, d3(*origin), ptr(ws), ptr(sums), st))
         f = sums.cpu().numpy()
         if not f[0] > 0:
-            return _empty(section, focus, radius, J, n_grid, **kwargs)
-        focus, radius = reference_sphere(f, origin, focus, radius)
+            return S
+        S.focus, S.radius = focus, radius = reference_sphere(f, origin, focus, radius)
 
     rays._dev["n"]  # (the index plane is written when it is read: this fills it if the trace left it stale)
     planes = torch.empty(3 * count, dtype=torch.float64, device=dev)
-    u, v, opl = planes[:count], planes[count:2 * count], planes[2 * count:]
-    w = torch.empty(count, dtype=torch.float32, device=dev)
-    missed = torch.zeros(1, dtype=torch.int64, device=dev)
+    S.u, S.v, S.opl = u, v, opl = planes[:count], planes[count:2 * count], planes[2 * count:]
+    S.w = w = torch.empty(count, dtype=torch.float32, device=dev)
+    S._res = torch.zeros(_capi.WF_M + 1 + extra, dtype=torch.float64, device=dev)
+    S.mom, S.missed, S.extra = S._res.split([_capi.WF_M, 1, extra])
+    S.missed = S.missed.view(torch.int64)
     _capi.check(lib.ot_wavefront_paths(C.byref(R), first, count, section, d3(*focus), radius, ptr(u), ptr(v), ptr(opl), ptr(w),
-                                       ptr(missed), st))
-    M, T, cells = _capi.WF_M, J * (J + 1) // 2 + J, n_grid * n_grid
-    res = torch.zeros(M + T + 2 * cells, dtype=torch.float64, device=dev)  # moments | normal equations | map sums
-    mom, zer, grid = res[:M], res[M:M + T], res[M + T:]
-    wl = rays._dev["wl"][first:first + count]
+                                       ptr(S.missed), st))
+    S.wl = wl = rays._dev["wl"][first:first + count]
+    _capi.check(lib.ot_wavefront_moments(count, ptr(u), ptr(v), ptr(opl), ptr(w), ptr(wl), ptr(ws), ptr(S.mom), st))
+    S.empty = False
+    return S
+
+
+def analyse(rays, first: int, count: int, section: int, origin, focus, radius, n_zernike: int, n_grid: int, pupil_radius,
+            **kwargs) -> WavefrontAnalysis:
+    """Figures of the rays [first, first + count) of the storage `rays` behind section `section`.  origin: a point near the
+    section's start that the device subtracts before it sums positions; the other arguments as `check_arguments` returned
+    them."""
+    from ._device import ptr, stream_ptr
+    lib = _capi.load_library()
+    J = n_zernike
+    T, cells = J * (J + 1) // 2 + J, n_grid * n_grid
+    S = sphere_stage(rays, first, count, section, origin, focus, radius, T + 2 * cells)  # extra: normal equations | map sums
+    focus, radius = S.focus, S.radius
+    if S.empty:
+        return _empty(section, focus, radius, J, n_grid, **kwargs)
+    st = stream_ptr()
+    u, v, opl, w, mom = ptr(S.u), ptr(S.v), ptr(S.opl), ptr(S.w), ptr(S.mom)
     pr = np.nan if pupil_radius is None else pupil_radius
-    _capi.check(lib.ot_wavefront_moments(count, ptr(u), ptr(v), ptr(opl), ptr(w), ptr(wl), ptr(ws), ptr(mom), st))
-    _capi.check(lib.ot_wavefront_map(count, ptr(u), ptr(v), ptr(opl), ptr(w), ptr(mom), pr, n_grid, ptr(grid), st))
-    _capi.check(lib.ot_wavefront_zernike(count, ptr(u), ptr(v), ptr(opl), ptr(w), ptr(mom), pr, J, ptr(ws), ptr(zer), st))
-    h = res.cpu().numpy()
-    n_missed = int(missed.cpu()[0])
-    m, packed, sums = h[:M], h[M:M + T], h[M + T:].reshape(2, n_grid, n_grid)
+    _capi.check(lib.ot_wavefront_map(count, u, v, opl, w, mom, pr, n_grid, ptr(S.extra[T:]), st))
+    _capi.check(lib.ot_wavefront_zernike(count, u, v, opl, w, mom, pr, J, ptr(S.ws), ptr(S.extra[:T]), st))
+    m, n_missed, h = S.read()
+    packed, sums = h[:T], h[T:].reshape(2, n_grid, n_grid)
     W = m[0]
     if not W > 0:
         return _empty(section, focus, radius, J, n_grid, n_missed, **kwargs)

@@ -355,9 +355,10 @@ def run_entry_points(x, y, w, fill, n, n_radii_list, freqs):
     return mom.cpu().numpy(), hists, otfs
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 1025, 70000])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1025, 70000, 2048 * 256 + 257])
 def test_entry_points_on_synthetic_lists(n):
-    """Sizes around a wave, a workgroup and the grid caps; frequency counts around the chunk of 8; radial bins in LDS and, above
+    """Sizes around a wave, a workgroup and the grid caps (the last one the first at which the cap of 2048 workgroups binds for
+    the moments, and every walker takes more than one step); frequency counts around the chunk of 8; radial bins in LDS and, above
     its budget, in global memory; dense and compact.  Tolerances as in `against_own_hits`."""
     x, y, w = synthetic(n)
     n_radii_list = [1, 32, LDS_BINS + 1808]

@@ -61,10 +61,13 @@ def test_detector_images_from_two_threads():
                 errors.append(e)
 
         threads = [threading.Thread(target=work, args=(s,)) for s in SEEDS]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
+        # (`no_warnings` is a process-wide switch: workers that leave it in another order than they entered it leave it off, and
+        # the tests after this one would see no warning.  Leaving it here, after them, puts it back.)
+        with ot.global_options.no_warnings():
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join()
         if errors:
             raise errors[0]
         for seed in SEEDS:  # the same calls, one thread
