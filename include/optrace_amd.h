@@ -796,6 +796,30 @@ int ot_psf_rays(const ot_rays* rays, int64_t first, int64_t count, int32_t secti
 int ot_psf_sum(int64_t n, const double* rec, double radius, int32_t n_px, double size, double dz, double* workspace, double* field,
                double* centre, void* stream);
 
+/* The same sum per band of the rays and per image plane (Raytracer.huygens_stack): rays of one band add coherently, bands add
+ * in intensity.  Checks and codes as above; n_bands above OT_PSF_MAX_BANDS, n_planes above OT_PSF_MAX_PLANES and a request
+ * whose workspace bound plus field exceeds OT_PSF_STACK_CAP doubles: OT_ERR_UNSUPPORTED.
+ * ot_psf_stack: rec[OT_PSF_REC * n] grouped, band b the records [starts[b], starts[b + 1]), starts[n_bands + 1] HOST, ascending
+ *   from 0 to n; plane z at dz[z], dz[n_planes] HOST.  field[n_planes][n_bands][2][n_px * n_px] = Re U | Im U of the band as
+ *   ot_psf_sum forms them; sums[n_planes][n_bands][5] = Re U, Im U on the axis | sum a | sum a^2 | sum a^2 kappa.  A band
+ *   without a record gives zeros.  One launch over (point tiles, ray chunks, planes): no chunk straddles a band, the chunk
+ *   length is that of ot_psf_sum for n records with its workgroups, times min(n_planes, 4), divided among the planes.  The result is a function of
+ *   rec, starts, n_px, size and dz alone; with one band and one plane it is ot_psf_sum's, bit for bit.
+ *   workspace >= ot_psf_stack_workspace(n, n_bands, n_px, n_planes) doubles, a bound that needs no starts (0 for arguments out
+ *   of range; with one band and one plane ot_psf_workspace(n, n_px)).
+ * ot_psf_combine: from field and sums, with W = sum a^2, A = sum a, kb = sum a^2 kappa / W and the bands with W > 0 in
+ *   ascending order: g[b] = W kb^2 / sum_c W_c kb_c^2 (0 for a band without a ray), band_strehl[n_planes][n_bands] = |U axis|^2 / A^2
+ *   (NaN for such a band), intensity[n_planes][n_px * n_px] = sum_b g_b |U|^2 / A_b^2, strehl[n_planes] = sum_b g_b band_strehl,
+ *   noise_floor[1] = sum_b g_b W_b / A_b^2. */
+#define OT_PSF_MAX_BANDS 32
+#define OT_PSF_MAX_PLANES 64
+#define OT_PSF_STACK_CAP ((int64_t)1 << 28)
+int64_t ot_psf_stack_workspace(int64_t n, int32_t n_bands, int32_t n_px, int32_t n_planes);
+int ot_psf_stack(int64_t n, const double* rec, int32_t n_bands, const int64_t* starts, double radius, int32_t n_px, double size,
+                 int32_t n_planes, const double* dz, double* workspace, double* field, double* sums, void* stream);
+int ot_psf_combine(int32_t n_bands, int32_t n_planes, int32_t n_px, const double* field, const double* sums, double* intensity,
+                   double* band_strehl, double* strehl, double* g, double* noise_floor, void* stream);
+
 /* ---- samplers: optrace/tracer/random.py, Surface.random_positions, color.random_wavelengths_from_srgb ---------
  * The samplers of the ray generator (ot_rays_generate) as entry points of their own: sample i of a call is what the
  * generator draws for ray i of a launch with the same seed and the same ranges -- counter-based dither keyed by (seed, i),

@@ -19,7 +19,7 @@ from .image import RGBImage, GrayscaleImage, ScalarImage
 from .render_image import RenderImage
 from .spot import SpotAnalysis
 from .wavefront import WavefrontAnalysis
-from .psf import HuygensPSF
+from .psf import HuygensPSF, HuygensStack
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
 from .convolve import convolve

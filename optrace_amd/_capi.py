@@ -199,6 +199,9 @@ SIGNATURES = {
     "ot_psf_workspace": (i64, [i64, i32]),
     "ot_psf_rays": (C.c_int, [C.POINTER(Rays), i64, i64, i32, C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp]),
     "ot_psf_sum": (C.c_int, [i64, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, vp]),
+    "ot_psf_stack_workspace": (i64, [i64, i32, i32, i32]),
+    "ot_psf_stack": (C.c_int, [i64, vp, i32, C.POINTER(i64), C.c_double, i32, C.c_double, i32, C.POINTER(C.c_double), vp, vp, vp, vp]),
+    "ot_psf_combine": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ot_sample_stratified": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(SourceRange), i32, u64, i64, vp, vp, vp]),
     "ot_sample_positions": (C.c_int, [C.POINTER(Source), C.POINTER(SourceRange), i32, u64, i64, vp, vp]),
     "ot_sample_inverse": (C.c_int, [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i64, vp, i64, C.POINTER(SourceRange), i32,
@@ -219,6 +222,7 @@ SAMPLE_DISCRETE, SAMPLE_CONTINUOUS = range(2)
 SPOT_M, SPOT_MAX_RADII, SPOT_MAX_FREQ = 8, 65536, 4096  # OT_SPOT_*
 WF_FOCUS_M, WF_M, WF_MAX_J, WF_MAX_GRID, WF_WS = 17, 11, 36, 1024, 40 * 2048  # OT_WF_*
 PSF_MAX_PX, PSF_REC = 1024, 6  # OT_PSF_*
+PSF_MAX_BANDS, PSF_MAX_PLANES, PSF_STACK_CAP = 32, 64, 1 << 28  # OT_PSF_MAX_BANDS, OT_PSF_MAX_PLANES, OT_PSF_STACK_CAP (doubles)
 
 
 def spot_ws(K: int) -> int:
@@ -235,6 +239,16 @@ def psf_ws(n: int, n_px: int) -> int:
     tiles = -(-points // 1024)
     chunks = max(1, min(1024 // tiles, -(-n // 128)))
     return chunks * (2 * points + 2)
+
+
+def psf_stack_ws(n: int, n_bands: int, n_px: int, n_planes: int) -> int:
+    """ot_psf_stack_workspace(n, n_bands, n_px, n_planes): doubles of workspace for ot_psf_stack, a bound that needs no starts.  The
+    workgroups aimed at, 1024 times min(n_planes, 4), are divided among the planes too; no chunk straddles a band, which costs n_bands - 1 chunks at the most.
+    With one band and one plane this is psf_ws(n, n_px)."""
+    points = n_px * n_px + 1
+    tiles = -(-points // 1024)
+    chunks = max(1, min(1024 * min(n_planes, 4) // (tiles * n_planes), -(-n // 128)))
+    return n_planes * (chunks + n_bands - 1) * (2 * points + 2)
 
 
 _lib = None

@@ -5,6 +5,10 @@ bundle to the reference sphere of the wavefront analysis.
 with the phase of its optical path, and the wavelets are added coherently at the points of an image plane around the focus.
 Definition: DESIGN.md, "Huygens PSF".  Kernels: csrc/ot_psf.hpp behind `ot_psf_rays` and `ot_psf_sum`; the paths and their mean
 come from `ot_wavefront_paths` and `ot_wavefront_moments` (wavefront.py).
+
+`Raytracer.huygens_stack` (second half of this file) does the same for a source of several wavelengths on several planes: rays of
+one band of wavelengths add coherently, bands add in intensity, behind `ot_psf_stack` and `ot_psf_combine`; `HuygensStack.mtf` is
+the diffraction MTF.  Definition: DESIGN.md, "Polychromatic through-focus PSF".
 """
 from __future__ import annotations
 
@@ -135,3 +139,292 @@ def analyse(rays, first: int, count: int, section: int, origin, focus, radius, n
                 "with its own: the point spread function is meaningful for a monochromatic source only.")
     intensity, strehl, noise_floor = figures(field.reshape(2, n_px, n_px), centre)
     return HuygensPSF(int(m[1]), W, n_missed, section, focus, radius, m[5] / W, size, dz, intensity, strehl, noise_floor, **kwargs)
+
+
+# ---- polychromatic, through focus: Raytracer.huygens_stack ---------------------------------------------------------------------------
+def check_stack_arguments(nt: int, section, focus, radius, n_px, size, dz, bands):
+    """Argument checks of `Raytracer.huygens_stack`, host only.  -> (focus, radius, size as `check_arguments` returns them, dz as a
+    float64 array (Z,), bands as "lines", an int or a float64 array of edges)."""
+    if isinstance(dz, (list, tuple, np.ndarray)):
+        planes = np.asarray(dz)
+        if planes.ndim != 1:
+            raise ValueError(f"Property 'dz' needs to be a number or a 1-D sequence, but has shape {planes.shape}.")
+        if not 1 <= planes.shape[0] <= _capi.PSF_MAX_PLANES:
+            raise ValueError(f"Property 'dz' needs to hold 1 to {_capi.PSF_MAX_PLANES} planes, but holds {planes.shape[0]}.")
+        planes = np.array([_wavefront._finite_number("dz", v) for v in planes.tolist()], dtype=np.float64)
+    else:
+        planes = np.array([_wavefront._finite_number("dz", dz)])
+    focus, radius, size, _ = check_arguments(nt, section, focus, radius, n_px, size, 0.0)
+    if isinstance(bands, str):
+        if bands != "lines":
+            raise ValueError(f"Property 'bands' needs to be 'lines', a number of bands or a sequence of edges, but is '{bands}'.")
+    elif isinstance(bands, (list, tuple, np.ndarray)):
+        edges = np.asarray(bands)
+        if edges.ndim != 1:
+            raise ValueError(f"Property 'bands' needs to be a 1-D sequence of edges, but has shape {edges.shape}.")
+        if not 2 <= edges.shape[0] <= _capi.PSF_MAX_BANDS + 1:
+            raise ValueError(f"Property 'bands' needs to hold 2 to {_capi.PSF_MAX_BANDS + 1} edges, but holds {edges.shape[0]}.")
+        bands = np.array([_wavefront._finite_number("bands", v) for v in edges.tolist()], dtype=np.float64)
+        if not np.all(np.diff(bands) > 0):
+            raise ValueError("Property 'bands' needs to hold strictly ascending edges.")
+    else:
+        check_type("bands", bands, int)
+        check_not_below("bands", bands, 1)
+        check_not_above("bands", bands, _capi.PSF_MAX_BANDS)
+    return focus, radius, size, planes, bands
+
+
+class DiffractionMTF(BaseClass):
+    """Result of `HuygensStack.mtf`: f (n_f,) in cycles / mm, mtf_x and mtf_y (n_f,), the modulus of the Fourier transform of the
+    line spread over x and over y, 1 at f = 0."""
+
+    _tracked = False
+
+    def __init__(self, f, mtf_x, mtf_y, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.f = np.array(f, dtype=np.float64)
+        self.mtf_x = np.array(mtf_x, dtype=np.float64)
+        self.mtf_y = np.array(mtf_y, dtype=np.float64)
+        self.lock()
+
+
+def diffraction_mtf(intensity, noise_floor: float, size: float, n_f: int = 65, f_max: float = None, **kwargs) -> DiffractionMTF:
+    """MTF of one plane of intensity (n_px, n_px) over a square of side `size` about the focus ("Polychromatic
+    through-focus PSF"): J = intensity - noise_floor, not clamped; its column sums are the line spread over x, its row sums the
+    one over y; OTF(f) = sum_c LSF[c] exp(-2 pi i f x_c) at the pixel centres x_c; MTF = |OTF(f)| / |OTF(0)|.  f_max: None for
+    the sampling limit n_px / (2 size), beyond which a ValueError is raised."""
+    check_type("n_f", n_f, int)
+    check_not_below("n_f", n_f, 1)
+    n_px = intensity.shape[0]
+    limit = n_px / (2 * size)
+    if f_max is None:
+        f_max = limit
+    else:
+        f_max = _wavefront._finite_number("f_max", f_max)
+        if f_max < 0 or f_max > limit:
+            raise ValueError(f"Property 'f_max' needs to lie in 0 .. {limit} cycles / mm, the sampling limit n_px / (2 size), but is {f_max}.")
+    f = np.linspace(0.0, f_max, n_f)
+    x = (np.arange(n_px) + 0.5 - n_px / 2) * (size / n_px)
+    J = intensity - noise_floor
+    kernel = np.exp(-2j * np.pi * f[:, None] * x[None])
+    otf_x, otf_y = kernel @ J.sum(axis=0), kernel @ J.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):  # (f[0] = 0: the first entry is OTF(0))
+        return DiffractionMTF(f, np.abs(otf_x) / np.abs(otf_x[0]), np.abs(otf_y) / np.abs(otf_y[0]), **kwargs)
+
+
+class HuygensStack(BaseClass):
+    """Result of `Raytracer.huygens_stack`: the Huygens PSF of a source of several wavelengths on several planes; lengths in mm.
+
+    Rays of one band add coherently, bands add in intensity ("Polychromatic through-focus PSF").  N, power: rays in
+    some band and their summed weight.  n_missed: as for `HuygensPSF`.  n_out_of_band: used rays whose wavelength lies in no
+    band.  section, focus (3), radius, size: as for `HuygensPSF`.  dz (Z,): the planes, at focus z + dz[z].  band_edges (K + 1,)
+    in nm, None for bands="lines"; band_N, band_power, band_wavelength (power-weighted mean, nm), band_weight (K,): the band
+    weight is W kappa_mean^2 over its sum, the share of a band's Strehl-normalised image in the irradiance.  intensity
+    (Z, n_px, n_px): sum_b weight_b |U_b|^2 / A_b^2, 1 at the focus when every band is a perfect wave focused there.
+    band_strehl (Z, K): |U_b|^2 / A_b^2 exactly on the axis (NaN for a band without a ray); strehl (Z,): its weighted sum.
+    noise_floor: sum_b weight_b W_b / A_b^2.  peak (Z,).  best_focus: dz of the first largest strehl.  Without a usable ray
+    N = power = 0, the arrays are NaN and every figure NaN."""
+
+    _tracked = False
+
+    def __init__(self, N: int, power: float, n_missed: int, n_out_of_band: int, section: int, focus, radius: float, size: float, dz,
+                 band_edges, band_N, band_power, band_wavelength, band_weight, intensity, strehl, band_strehl, noise_floor: float,
+                 **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.N = int(N)
+        self.power = float(power)
+        self.n_missed = int(n_missed)
+        self.n_out_of_band = int(n_out_of_band)
+        self.section = int(section)
+        self.focus = np.array(focus, dtype=np.float64)
+        self.radius = float(radius)
+        self.size = float(size)
+        self.dz = np.array(dz, dtype=np.float64)
+        self.band_edges = None if band_edges is None else np.array(band_edges, dtype=np.float64)
+        self.band_N = np.array(band_N, dtype=np.int64)
+        self.band_power = np.array(band_power, dtype=np.float64)
+        self.band_wavelength = np.array(band_wavelength, dtype=np.float64)
+        self.band_weight = np.array(band_weight, dtype=np.float64)
+        self.intensity = np.array(intensity, dtype=np.float64)
+        self.strehl = np.array(strehl, dtype=np.float64)
+        self.band_strehl = np.array(band_strehl, dtype=np.float64)
+        self.noise_floor = float(noise_floor)
+        self.peak = self.intensity.max(axis=(1, 2)) if self.N else np.full(self.dz.shape[0], np.nan)
+        self.best_focus = float(self.dz[int(np.argmax(self.strehl))]) if self.N else np.nan
+        self.lock()
+
+    @property
+    def wavelength(self) -> float:
+        """Power-weighted mean wavelength of the rays in some band, nm."""
+        return float((self.band_power * self.band_wavelength)[self.band_N > 0].sum() / self.power) if self.N else np.nan
+
+    def psf(self, z: int = 0) -> HuygensPSF:
+        """Plane z as a `HuygensPSF`."""
+        z = self._plane(z)
+        return HuygensPSF(self.N, self.power, self.n_missed, self.section, self.focus, self.radius, self.wavelength, self.size,
+                          self.dz[z], self.intensity[z], self.strehl[z], self.noise_floor, long_desc=self.long_desc)
+
+    def to_image(self, z: int = 0) -> GrayscaleImage:
+        """`HuygensPSF.to_image` of plane z."""
+        return self.psf(z).to_image()
+
+    def mtf(self, z: int = 0, n_f: int = 65, f_max: float = None) -> DiffractionMTF:
+        """Diffraction MTF of plane z along x and y at n_f frequencies from 0 to f_max (None: the sampling limit n_px / (2 size));
+        host arithmetic on `intensity[z]`, see `diffraction_mtf`."""
+        return diffraction_mtf(self.intensity[self._plane(z)], self.noise_floor, self.size, n_f, f_max, long_desc=self.long_desc)
+
+    def _plane(self, z) -> int:
+        check_type("z", z, int)
+        check_not_below("z", z, 0)
+        check_not_above("z", z, self.dz.shape[0] - 1)
+        return z
+
+
+def _empty_stack(section: int, focus, radius, n_px: int, size, dz, bands, n_missed: int = 0, n_out_of_band: int = 0,
+                 **kwargs) -> HuygensStack:
+    """(the rule of `_empty`: what the caller fixed stays; bands given as edges keep them, else one band without a ray)"""
+    nan, Z = np.nan, dz.shape[0]
+    edges = bands if isinstance(bands, np.ndarray) else None
+    K = 1 if edges is None else edges.shape[0] - 1
+    return HuygensStack(0, 0.0, n_missed, n_out_of_band, section, np.full(3, nan) if focus is None else focus,
+                        nan if radius is None else radius, nan if size is None else size, dz, edges, np.zeros(K), np.zeros(K),
+                        np.full(K, nan), np.full(K, nan), np.full((Z, n_px, n_px), nan), np.full(Z, nan), np.full((Z, K), nan), nan,
+                        **kwargs)
+
+
+def assign_bands(wl, live, bands):
+    """Band index per ray, on the device of `wl`.  wl: float32 wavelengths; live: which rays take part at all; bands: as
+    `check_stack_arguments` returns them.  -> (key int64, K for rays in no band; K as asked for; table float64: the K + 1 edges,
+    or for "lines" the 32 smallest lines padded with inf behind one slot that holds the number of lines)
+
+    A wavelength is compared as float64 with float64 edges: band b holds e[b] <= wl < e[b + 1], the last band its upper edge too.
+    An int K means K equal bands over [min, max] of the live rays; with min == max every live ray lies on the last edge and so
+    in band K - 1, which `group_records`' caller reads as the one band there is."""
+    import torch
+    w64 = wl.to(torch.float64)
+    if isinstance(bands, str):
+        lines = torch.unique(wl[live]).to(torch.float64)  # ascending
+        K = _capi.PSF_MAX_BANDS
+        n_lines = lines.shape[0]
+        table = torch.full((K + 1,), torch.inf, dtype=torch.float64, device=wl.device)
+        table[0] = n_lines
+        table[1:1 + min(n_lines, K)] = lines[:K]
+        key = torch.searchsorted(table[1:].contiguous(), w64).clamp(max=K)  # (a live ray's wavelength is a line: found exactly)
+        return torch.where(live, key, K), K, table
+    if isinstance(bands, np.ndarray):
+        edges = torch.as_tensor(bands, device=wl.device)
+    else:
+        lo = torch.where(live, w64, torch.inf).amin()
+        hi = torch.where(live, w64, -torch.inf).amax()
+        edges = lo + (hi - lo) * (torch.arange(bands + 1, dtype=torch.float64, device=wl.device) / bands)
+        edges[-1] = hi
+    K = edges.shape[0] - 1
+    key = torch.bucketize(w64, edges, right=True) - 1  # e[key] <= wl < e[key + 1]; -1 below all, K from the last edge on
+    key = torch.where(w64 == edges[-1], K - 1, key)
+    return torch.where(live & (key >= 0) & (key < K), key, K), K, edges
+
+
+def group_records(rec, count: int, key, K: int, table):
+    """Stable group-by of the record planes rec (6 * count) by `key`: band b in ascending ray order, rays with key K dropped.  One
+    read of the device: the K + 1 starts and `table`.  -> (grouped (6 * n) device, starts (K + 1,) int64 host, table host, the
+    n grouped rays' indices device)"""
+    import torch
+    order = torch.sort(key, stable=True).indices
+    counts = torch.bincount(key, minlength=K + 1)[:K]
+    head = torch.cat([torch.zeros(1, dtype=torch.float64, device=key.device), counts.cumsum(0).to(torch.float64), table]).cpu().numpy()
+    starts = head[:K + 1].astype(np.int64)
+    order = order[:int(starts[-1])]
+    return rec.view(_capi.PSF_REC, count)[:, order].contiguous().view(-1), starts, head[K + 1:], order
+
+
+def settle_bands(bands, K: int, starts, table):
+    """What the host makes of the starts and the table of `assign_bands` once it has read them.  -> (K, starts, band_edges): for
+    "lines" the number of lines found (one band where there is no ray) and no edges, for an int the edges, or one band from
+    min to max where they are equal.  More than 32 lines: RuntimeError."""
+    if isinstance(bands, str):
+        if table[0] > K:
+            raise RuntimeError(f"The used rays carry {int(table[0])} distinct wavelengths, more than the {K} that bands='lines' "
+                               "takes: pass band edges or a number of bands.")
+        K = max(int(table[0]), 1)
+        return K, starts[:K + 1], None
+    if starts[-1] and not isinstance(bands, np.ndarray) and table[0] == table[-1]:
+        return 1, starts[[0, -1]], table[[0, -1]]
+    return K, starts, table
+
+
+def check_cap(n: int, K: int, n_px: int, Z: int) -> None:
+    """The limit of `ot_psf_stack` on workspace plus field, said before anything of that size is asked of the device."""
+    if _capi.psf_stack_ws(n, K, n_px, Z) + Z * K * 2 * n_px * n_px > _capi.PSF_STACK_CAP:
+        raise RuntimeError(f"{Z} planes x {K} bands x {n_px}^2 image points need more than {_capi.PSF_STACK_CAP} doubles on the device: "
+                           "ask for fewer planes, bands or image points per call.")
+
+
+def call_stack(grouped, starts, radius: float, n_px: int, size: float, dz, out) -> None:
+    """`ot_psf_stack` and `ot_psf_combine` on grouped records, the figures into the device buffer `out` of `stack_parts(K, Z, n_px)`
+    doubles."""
+    import torch
+    from ._device import ptr, stream_ptr
+    lib = _capi.load_library()
+    K, Z, n, st = starts.shape[0] - 1, dz.shape[0], int(starts[-1]), stream_ptr()
+    parts = stack_parts(K, Z, n_px)
+    check_cap(n, K, n_px, Z)
+    inten, bs, s, g, floor, sums = out[:sum(parts)].split(parts)
+    ws = torch.empty(_capi.psf_stack_ws(n, K, n_px, Z), dtype=torch.float64, device=grouped.device)
+    field = torch.empty(Z * K * 2 * n_px * n_px, dtype=torch.float64, device=grouped.device)
+    _capi.check(lib.ot_psf_stack(n, ptr(grouped), K, (C.c_int64 * (K + 1))(*starts.tolist()), radius, n_px, size, Z,
+                                 (C.c_double * Z)(*dz.tolist()), ptr(ws), ptr(field), ptr(sums), st))
+    _capi.check(lib.ot_psf_combine(K, Z, n_px, ptr(field), ptr(sums), ptr(inten), ptr(bs), ptr(s), ptr(g), ptr(floor), st))
+
+
+def stack_parts(K: int, Z: int, n_px: int):
+    """doubles of intensity | band_strehl | strehl | g | noise_floor | sums in the result buffer of `call_stack`"""
+    return [Z * n_px * n_px, Z * K, Z, K, 1, Z * K * 5]
+
+
+def analyse_stack(rays, first: int, count: int, section: int, origin, focus, radius, n_px: int, size, dz, bands, **kwargs) -> HuygensStack:
+    """`analyse` for bands of wavelengths and several planes; the arguments as `check_stack_arguments` returned them.  Besides the
+    reads of `analyse` before the sum, the host reads the band starts; everything else comes in one buffer at the end."""
+    import torch
+    from ._device import ptr, stream_ptr
+    lib = _capi.load_library()
+    Z = dz.shape[0]
+    K_max = _capi.PSF_MAX_BANDS if isinstance(bands, str) else bands.shape[0] - 1 if isinstance(bands, np.ndarray) else bands
+    check_cap(count, 1 if isinstance(bands, str) else K_max, n_px, Z)  # (with "lines" the bands are known later: `call_stack`)
+    S = _wavefront.sphere_stage(rays, first, count, section, origin, focus, radius, sum(stack_parts(K_max, Z, n_px)) + K_max)
+    focus, radius = S.focus, S.radius
+    if S.empty:
+        return _empty_stack(section, focus, radius, n_px, size, dz, bands, **kwargs)
+    if size is None:
+        m = S.mom.cpu().numpy()
+        if not m[0] > 0:
+            return _empty_stack(section, focus, radius, n_px, size, dz, bands, int(S.missed.cpu()[0]), **kwargs)
+        size = default_size(m)
+        if not (np.isfinite(size) and size > 0):
+            raise RuntimeError("The used rays meet the reference sphere in one place, which gives the image no scale: pass `size`.")
+    rec = torch.empty(_capi.PSF_REC * count, dtype=torch.float64, device=S.w.device)
+    _capi.check(lib.ot_psf_rays(C.byref(S.R), first, count, section, (C.c_double * 3)(*focus), radius, ptr(S.opl), ptr(S.mom),
+                                ptr(rec), stream_ptr()))
+    live = rec[5 * count:] != 0  # (the plane of a)
+    key, K, table = assign_bands(S.wl, live, bands)
+    n_live = live.sum().to(torch.float64).reshape(1)
+    grouped, starts, table, order = group_records(rec, count, key, K, torch.cat([table, n_live]))
+    table, n_live = table[:-1], int(table[-1])
+    n = int(starts[-1])
+    K, starts, edges = settle_bands(bands, K, starts, table)
+    if not n:
+        n_missed = S.read()[1]
+        return _empty_stack(section, focus, radius, n_px, size, dz, bands, n_missed, n_live, **kwargs)
+    parts = stack_parts(K, Z, n_px)
+    call_stack(grouped, starts, radius, n_px, size, dz, S.extra)
+    if edges is not None:  # power-weighted mean wavelength per band: sum a^2 wl over its rays, behind the figures in the result buffer
+        a2wl = grouped[5 * n:] ** 2 * S.wl.to(torch.float64)[order]
+        for b in range(K):
+            S.extra[sum(parts) + b] = a2wl[starts[b]:starts[b + 1]].sum()
+    _, n_missed, h = S.read()
+    inten, bs, s, g, floor, sums, band_wl = np.split(h[:sum(parts) + K], np.cumsum(parts))
+    sums = sums.reshape(Z, K, 5)
+    W = sums[0, :, 3]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        band_wl = table[1:K + 1] if edges is None else band_wl / W  # (a line is its own mean)
+    return HuygensStack(n, W.sum(), n_missed, n_live - n, section, focus, radius, size, dz, edges, np.diff(starts), W, band_wl, g,
+                        inten.reshape(Z, n_px, n_px), s, bs.reshape(Z, K), floor[0], **kwargs)

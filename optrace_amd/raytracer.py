@@ -36,7 +36,7 @@ from .spot import SpotAnalysis
 from . import wavefront as _wavefront
 from .wavefront import WavefrontAnalysis
 from . import psf as _psf
-from .psf import HuygensPSF
+from .psf import HuygensPSF, HuygensStack
 from .geometry.ray_source import RaySource
 from .scene import CompiledScene, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
@@ -829,12 +829,27 @@ class Raytracer(Group):
         spherical wavelet from its place on the reference sphere of `wavefront_analysis`, with the phase of its optical path, and
         the wavelets are added coherently on the GPU (psf.py).  section, focus, radius: as for `wavefront_analysis`; n_px: image
         points per side; size: side length of the square of image points about the focus in the plane z = focus z + dz, default
-        ten mean wavelengths over the pupil radius (about eight Airy diameters in air)."""
+        ten mean wavelengths over the pupil radius (about eight Airy diameters in air).  For a source of several wavelengths or
+        several planes: `huygens_stack`."""
         nt = len(self.tracing_surfaces) + 2
         focus, radius, size, dz = _psf.check_arguments(nt, section, focus, radius, n_px, size, dz)
         Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the point spread function holds")
         return _psf.analyse(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_px, size, dz,
                             long_desc=f"Huygens PSF of {label} behind section {k}")
+
+    def huygens_stack(self, source_index: int = 0, section: int = None, focus=None, radius: float = None, n_px: int = 64,
+                      size: float = None, dz=0.0, bands="lines") -> HuygensStack:
+        """`huygens_psf` for a source of several wavelengths, on one plane or a through-focus series: rays of one band of
+        wavelengths add coherently, the bands add in intensity, each with the weight of its power and (n / lambda)^2 (psf.py).
+        dz: a number or up to 64 of them, plane z lies at focus z + dz[z].  bands: "lines", every distinct wavelength a band of its
+        own (32 at the most); an int K, that many equal bands over the used rays' wavelengths; or K + 1 ascending edges in nm,
+        the last band closed above.  The other arguments as for `huygens_psf`.  The result also gives the diffraction MTF
+        (`HuygensStack.mtf`)."""
+        nt = len(self.tracing_surfaces) + 2
+        focus, radius, size, dz, bands = _psf.check_stack_arguments(nt, section, focus, radius, n_px, size, dz, bands)
+        Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the point spread function holds")
+        return _psf.analyse_stack(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_px, size, dz, bands,
+                                  long_desc=f"Huygens PSF stack of {label} behind section {k}")
 
     def _section_bundle(self, source_index, section, holds: str):
         """What the analyses of a stored section share, after their own argument checks: the device, current rays, the ray range
