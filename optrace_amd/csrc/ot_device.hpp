@@ -402,7 +402,21 @@ OT_DEV void handle_abnormal_f(SF& sf, const V3& p, const V3& s, V3& ph, bool& hi
     }
 }
 
-// ConicSurface.find_hit conic_surface.py:126-203 (closed-form quadratic)
+// ConicSurface.find_hit conic_surface.py:126-203 (closed-form quadratic): the reference's root selection and no-hit rules
+// on the two roots of A t^2 + 2 B t + C = 0, with its B, C, A and D, but not its (-B -+ D) / A: that cancels in the
+// numerator and divides what is left by A -- for a paraboloid A = sin^2 of the angle to the axis, so a beam 2^-20 off
+// the axis is off by 0.75 mm or loses the hit altogether, and -B - D cancels for any conic of large radius (DESIGN.md,
+// "The hit step at its edges").  Here q = -(B + sign(B) D), roots q / A and C / q: no difference of nearly equal numbers,
+// and C / q stays finite where A goes through zero.  At A == 0 (a ray along the axis of a paraboloid) q = -2 B and C / q
+// is the reference's linear root -C / (2 B) bit for bit, q / A is no number and fails every test: the reference's branch
+// for that case is this one.  tests/hit_cases.py::stable_form restates this in NumPy; tests/test_gpu_hit_step.py holds it
+// to exact intersections.  Spheres of |R| <= OT_PLAIN_SPHERE_R keep the reference's -B -+ D, bit for bit: A = 1 there, so
+// all it loses is 2 u |R| in the numerator, at most 2^-40 mm, and the trace kernel is bound by f64 issue -- the quotient
+// C / q on every sphere costs the double-Gauss benchmark 4.3 %, on its four surfaces of |R| > 256 mm still 2.1 %
+// (profiles/hit_step).  Flatter spheres, where that loss grows to 6e-10 mm at R = 1e7, take the stable roots with A = 1.
+// (D itself is the reference's: B B - C A still loses u |o|^2 / (2 D) for a start far from a
+// strongly curved surface, see hit_cases.py on `far`.)
+#define OT_PLAIN_SPHERE_R 4096.0  // mm
 template <class SF>
 OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) {
     double ox = p.x - sf.px, oy = p.y - sf.py, oz = p.z - sf.pz;
@@ -411,16 +425,19 @@ OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) 
     double B = s.x * ox + s.y * oy + s.z * (ozk - sf.inv_rho);
     double C = oy * oy + ox * ox + oz * (ozk - sf.two_inv_rho);
     double A = 1.0, D, t1, t2;
-    if (sphere) {  // A = 1.0: C * 1.0 == C and x / 1.0 == x exactly, so both are skipped
+    if (sphere && fabs(sf.inv_rho) <= OT_PLAIN_SPHERE_R) {  // wave-uniform; A = 1.0: C * 1.0 == C, x / 1.0 == x exactly
         D = ot_sqrt(B * B - C);
         t1 = -B - D;
         t2 = -B + D;
     } else {
-        A = 1 + sf.k * (s.z * s.z);
+        if (!sphere) A = 1 + sf.k * (s.z * s.z);
         D = ot_sqrt(B * B - C * A);
-        const double iA = ot_rcp3(A);
-        t1 = ot_div_r(-B - D, A, iA);
-        t2 = ot_div_r(-B + D, A, iA);
+        const bool bp = B >= 0;
+        const double q = -(B + (bp ? D : -D));
+        const double ta = ot_div(q, A);
+        const double tb = (q == 0) ? ta : ot_div(C, q);  // B == 0 and D == 0: a double root at 0 / A
+        t1 = bp ? ta : tb;  // (-B - D) / A
+        t2 = bp ? tb : ta;  // (-B + D) / A
     }
     double z = p.z;
     double z1 = z + s.z * t1;
@@ -430,11 +447,6 @@ OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) 
     double t = (c1 && !c2) ? t1 : t2;
     ph = along(p, s, t);
     hit = surf_mask<false>(sf, ph.x, ph.y);
-    if (!sphere && A == 0 && B != 0) {
-        t = -C / (2 * B);
-        ph = along(p, s, t);
-        hit = surf_mask<false>(sf, ph.x, ph.y);
-    }
     bool nh = !hit || !isfinite(D) || (!sphere && A == 0 && B == 0) || (ph.z < sf.z_lo) || (ph.z > sf.z_hi);
     if (nh) {
         double tnh = (sf.z_max - p.z) / s.z;

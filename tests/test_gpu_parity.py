@@ -11,6 +11,7 @@ import optrace_amd as ot
 from optrace_amd import _capi
 from optrace_amd.scene import CompiledScene
 
+import hit_cases as hc
 import oracle_bridge as ob
 import scenes
 from helpers import load, assert_close, sparse_to_dense, image_rel_l1
@@ -52,11 +53,21 @@ def test_find_hit(zoo, leaf, name):
         assert np.array_equal(ill, leaf[f"{name}/ill"])
     else:
         assert not leaf[f"{name}/ill"].any()
-    assert_close(ph, leaf[f"{name}/p_hit"], rtol=1e-12, atol=1e-12, what=f"{name} p_hit")
+    keep = np.ones(ph.shape[0], dtype=bool)
+    if name == "conic_parab":
+        # The reference's closed form divides a cancelling numerator by A = sin^2 of the ray's angle to a paraboloid's axis:
+        # at the small tilts among these rays its recorded hit is farther from the exact one (mpmath,
+        # tests/golden/generate_golden_hit_step.py) than this test's 1e-12, and the oracle follows it.  Exactly those rays
+        # are held to the exact hit with the bar of tests/hit_cases.py instead; masks stay bit-equal on all of them.
+        g = load("hit_step.npz")
+        idx, ratio = hc.zoo_parab_check(g, leaf[f"{name}/p"], leaf[f"{name}/s"], ph)
+        assert np.array_equal(sf.pos, g["zoo_parab/geom"][:3]) and ratio <= 1, ratio
+        keep[idx] = False
+    assert_close(ph[keep], leaf[f"{name}/p_hit"][keep], rtol=1e-12, atol=1e-12, what=f"{name} p_hit")
     # against the oracle as well (same inputs)
     ph_o, hit_o, ill_o, st = ob.find_hit(sf._desc(), leaf[f"{name}/p"], leaf[f"{name}/s"])
     assert np.array_equal(hit, hit_o)
-    assert_close(ph, ph_o, rtol=1e-12, atol=1e-12, what=f"{name} p_hit vs oracle")
+    assert_close(ph[keep], ph_o[keep], rtol=1e-12, atol=1e-12, what=f"{name} p_hit vs oracle")
 
 
 @pytest.mark.parametrize("name", SURFACE_NAMES)
