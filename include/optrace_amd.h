@@ -820,6 +820,25 @@ int ot_psf_stack(int64_t n, const double* rec, int32_t n_bands, const int64_t* s
 int ot_psf_combine(int32_t n_bands, int32_t n_planes, int32_t n_px, const double* field, const double* sums, double* intensity,
                    double* band_strehl, double* strehl, double* g, double* noise_floor, void* stream);
 
+/* ---- field-dependent convolution (ot.convolve_field; no counterpart in optrace) -----------------------------------
+ * An image spread by a gy x gx grid of point spread functions, one per field point, blended bilinearly over the image's
+ * interior: the PSF belongs to the SOURCE pixel.  Planar layouts: img[n_ch][ny][nx], psf[gy][gx][py][px],
+ * out[n_ch][ny + py - 1][nx + px - 1], the full convolution.  The interior is the rectangle [y0, y0 + ny_in) x
+ * [x0, x0 + nx_in) of the plane; pixels outside it (a padding rim) take the weights of the nearest interior pixel.  Node
+ * (b, a) belongs to the interior's row fraction b / (gy - 1) and column fraction a / (gx - 1).  With hat(u) = max(0, 1 - |u|),
+ *   t_x(i) = clamp((i - x0) / (nx_in - 1), 0, 1) (gx - 1)   (0 when gx = 1 or nx_in = 1; t_y alike),
+ *   W[b][a](j, i) = hat(t_y(j) - b) hat(t_x(i) - a),
+ *   out[c][y][x] = sum_{b,a} sum_{dy,dx} psf[b][a][dy][dx] W[b][a](y - dy, x - dx) img[c][y - dy][x - dx]
+ * over the taps with 0 <= y - dy < ny, 0 <= x - dx < nx.  Pointers are DEVICE; the launch is ordered on `stream` and nothing is
+ * waited for.  A null pointer, n_ch outside 1..3, a size below 1, an interior that is not inside the plane: OT_ERR_INVALID;
+ * py or px above OT_CONVF_MAX_PSF, gy or gx above OT_CONVF_MAX_GRID, an output plane above 2^31 - 1 elements:
+ * OT_ERR_UNSUPPORTED; all before a device is looked for.  Every output element is written once by one lane, its terms added in
+ * f64 with fused multiply-adds in an order fixed by the shapes alone: the same call returns the same bits. */
+#define OT_CONVF_MAX_PSF 512  /* py, px */
+#define OT_CONVF_MAX_GRID 64  /* gy, gx */
+int ot_convolve_field(const double* img, int32_t n_ch, int32_t ny, int32_t nx, int32_t y0, int32_t x0, int32_t ny_in,
+                      int32_t nx_in, const double* psf, int32_t gy, int32_t gx, int32_t py, int32_t px, double* out, void* stream);
+
 /* ---- samplers: optrace/tracer/random.py, Surface.random_positions, color.random_wavelengths_from_srgb ---------
  * The samplers of the ray generator (ot_rays_generate) as entry points of their own: sample i of a call is what the
  * generator draws for ray i of a launch with the same seed and the same ranges -- counter-based dither keyed by (seed, i),

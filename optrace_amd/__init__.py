@@ -22,7 +22,7 @@ from .wavefront import WavefrontAnalysis
 from .psf import HuygensPSF, HuygensStack
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
-from .convolve import convolve
+from .convolve import convolve, convolve_field
 from .tma import TMA
 from .load import load_agf, load_zmx
 from . import presets, misc, color, random

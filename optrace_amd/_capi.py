@@ -202,6 +202,7 @@ SIGNATURES = {
     "ot_psf_stack_workspace": (i64, [i64, i32, i32, i32]),
     "ot_psf_stack": (C.c_int, [i64, vp, i32, C.POINTER(i64), C.c_double, i32, C.c_double, i32, C.POINTER(C.c_double), vp, vp, vp, vp]),
     "ot_psf_combine": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ot_convolve_field": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]),
     "ot_sample_stratified": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(SourceRange), i32, u64, i64, vp, vp, vp]),
     "ot_sample_positions": (C.c_int, [C.POINTER(Source), C.POINTER(SourceRange), i32, u64, i64, vp, vp]),
     "ot_sample_inverse": (C.c_int, [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i64, vp, i64, C.POINTER(SourceRange), i32,
@@ -223,6 +224,7 @@ SPOT_M, SPOT_MAX_RADII, SPOT_MAX_FREQ = 8, 65536, 4096  # OT_SPOT_*
 WF_FOCUS_M, WF_M, WF_MAX_J, WF_MAX_GRID, WF_WS = 17, 11, 36, 1024, 40 * 2048  # OT_WF_*
 PSF_MAX_PX, PSF_REC = 1024, 6  # OT_PSF_*
 PSF_MAX_BANDS, PSF_MAX_PLANES, PSF_STACK_CAP = 32, 64, 1 << 28  # OT_PSF_MAX_BANDS, OT_PSF_MAX_PLANES, OT_PSF_STACK_CAP (doubles)
+CONVF_MAX_PSF, CONVF_MAX_GRID = 512, 64  # OT_CONVF_MAX_PSF, OT_CONVF_MAX_GRID
 
 
 def spot_ws(K: int) -> int:

@@ -16,6 +16,10 @@ scipy.signal.fftconvolve(mode="full") pads to the next 5-smooth length and multi
 so results agree to rounding (tests/test_gpu_convolve.py against fixtures computed by the reference itself).
 The reference resizes the PSF with cv2.resize(INTER_AREA) (convolve.py:335); here the area average is formed from
 the pixel overlaps directly (identity when PSF and image share a pixel pitch, block means for integer ratios).
+
+convolve_field() is the same image formation with a PSF per field point, blended bilinearly over the image (DESIGN.md,
+"Field-dependent convolution").  It shares every step with convolve() but the convolution itself, which is no FFT product: the
+direct sum runs in one HIP kernel, `ot_convolve_field` (csrc/ot_convolve.hpp).
 """
 from __future__ import annotations
 
@@ -71,34 +75,20 @@ def _gamma(v: torch.Tensor) -> torch.Tensor:
     return torch.where(av <= 0.0031308, v * 12.92, torch.sign(v) * ((1 + a) * av ** (1 / 2.4) - a))
 
 
-def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str = "constant", padding_value=None,
-             cargs: dict = {}):
-    """Convolve an image with a point spread function (same signature, cases and errors as the reference's).
+# ---- steps shared by convolve() and convolve_field() -------------------------------------------------------------------
 
-    1. GrayscaleImage with a GrayscaleImage PSF -> GrayscaleImage
-    2. GrayscaleImage with a RenderImage PSF (colour information in the PSF) -> RGBImage
-    3. RGBImage with a GrayscaleImage PSF -> RGBImage
-    4. RGBImage with a list of three RenderImage PSFs, rendered for the sRGB R, G, B primaries -> RGBImage
-
-    `m` scales the image before the convolution (|m| > 1 enlarges, m < 0 flips it).  `padding_mode` is one of
-    numpy.pad's modes, `padding_value` (three values for an RGBImage, one otherwise) belongs to "constant".
-    `keep_size` crops the result back to the pixel count of the input.  `cargs` overrides the arguments of the final
-    colour mapping, by default rendering_intent="Absolute", normalize=True, clip=True, L_th=0, chroma_scale=None.
-    """
+def _check_arguments(img, m, keep_size, cargs) -> None:
     check_type("m", m, (int, float))
     check_type("cargs", cargs, dict)
     check_above("abs(m)", abs(m), 0)
     check_type("keep_size", keep_size, bool)
     check_type("img", img, (RGBImage, GrayscaleImage))
 
-    img_color = isinstance(img, RGBImage)
-    gray_only = isinstance(psf, GrayscaleImage) and not img_color  # one plane in, one plane out
-    three_psf = isinstance(psf, list) and len(psf) == 3
-    psf_color = isinstance(psf, RenderImage) or three_psf
-    dev = require_device()
 
-    # ---- image: padding value and gamma removal (convolve.py:156-203) ----------------------------------------
-    if img_color:
+def _image_input(img, padding_mode, padding_value):
+    """Padding value and gamma removal (convolve.py:156-203) -> (planes (Ny, Nx, 3) or (Ny, Nx), linear padding value (3),
+    whether the padding is anything but plain zero)."""
+    if isinstance(img, RGBImage):
         check_type("padding_value", padding_value, (list, np.ndarray, type(None)))
         pval = np.zeros(3) if padding_value is None else np.asarray(padding_value, dtype=np.float64)
         if pval.ndim != 1 or pval.shape[0] != 3:
@@ -113,29 +103,20 @@ def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str 
     pval_lin = srgb_to_srgb_linear(pval.copy())
     planes = srgb_to_srgb_linear(img.data)  # (Ny, Nx, 3) or (Ny, Nx)
     custom_padding = not (padding_mode == "constant" and float(pval_lin.sum()) == 0)
+    return planes, pval_lin, custom_padding
 
-    # ---- PSF checks (convolve.py:206-253) ----------------------------------------------------------------------
-    if psf_color:
-        psfs = psf if three_psf else [psf]
-        if img_color and not three_psf:
-            raise TypeError("A list of a R, G, B RenderImage PSF is required for convolving"
-                            " a colored image with a colored PSF.")
-        if not img_color and three_psf:
-            raise TypeError("A single colored RenderImage is sufficient for a grayscale image.")
-        for i, p_i in enumerate(psfs):
-            check_type(f"psf[{i}]", p_i, RenderImage)
-            if not np.all(np.asarray(psfs[0].extent) == np.asarray(p_i.extent)):
-                raise ValueError("All PSF sizes need to be the same. Render the detector image with"
-                                 " the same manual extent option.")
-    else:
-        check_type("psf", psf, GrayscaleImage)
-        psfs = [psf]
 
-    # ---- sizes (convolve.py:256-339): pixel centres span the side lengths, so pitch = s / (n - 1) ------------
+class _Sizes:
+    """Pixel counts ([x, y] pairs) and the result extent of one call (convolve.py:256-339)."""
+
+
+def _sizes(img, psf0, m, keep_size, custom_padding) -> _Sizes:
+    """Size checks and warnings of the image and one PSF (all PSFs of a call share shape and extent); pixel centres span the
+    side lengths, so pitch = s / (n - 1)."""
     iN = np.array([img.shape[1], img.shape[0]])
-    pN = np.array([psfs[0].shape[1], psfs[0].shape[0]])
+    pN = np.array([psf0.shape[1], psf0.shape[0]])
     is_ = np.array(img.s) * abs(m)
-    ps_ = np.array(psfs[0].s)
+    ps_ = np.array(psf0.s)
     ip, pp = is_ / (iN - 1), ps_ / (pN - 1)
     if ps_[0] > 2 * is_[0] or ps_[1] > 2 * is_[1]:
         raise ValueError(f"m-scaled image size [{is_[0]:.5g}, {is_[1]:.5g}] is more than two times "
@@ -148,7 +129,7 @@ def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str 
         warning(f"PSF pixel sizes [{pp[0]:.5g}, {pp[1]:.5g}] larger than image pixel sizes"
                 f" [{ip[0]:.5g}, {ip[1]:.5g}], generally you want a PSF in a higher resolution")
     if pN[0] < 50 or pN[1] < 50:
-        raise ValueError(f"PSF too small with shape {psfs[0].shape}, "
+        raise ValueError(f"PSF too small with shape {psf0.shape}, "
                          "needs to have at least 50 values in each dimension.")
     if iN[0] < 50 or iN[1] < 50:
         raise ValueError(f"Image too small with shape {img.shape}, needs to have at least 50 values in each dimension.")
@@ -161,20 +142,26 @@ def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str 
     if not (0.2 < ip[0] / ip[1] < 5):
         warning(f"Pixels of image are strongly non-square with side lengths [{ip[0]}mm, {ip[1]}mm]")
 
+    z = _Sizes()
+    z.iN, z.pN = iN, pN
     sc = pp / ip
-    ppad = 4                                                            # zero rim around the resized PSF
-    p2N = np.where(pN * sc < 1, 1, np.round(pN * sc).astype(int))       # PSF pixels at the image's pitch
-    p3N = p2N + 2 * ppad
-    ipad = p3N if custom_padding else np.array([0, 0])                  # image rim for the padding mode
-    i2N = iN + 2 * ipad
-    i3N = i2N + p3N - 1                                                 # "full" convolution
-    i4N = iN if keep_size else iN + p3N - 1
+    z.ppad = 4                                                            # zero rim around the resized PSF
+    z.p2N = np.where(pN * sc < 1, 1, np.round(pN * sc).astype(int))       # PSF pixels at the image's pitch
+    z.p3N = z.p2N + 2 * z.ppad
+    z.ipad = z.p3N if custom_padding else np.array([0, 0])                # image rim for the padding mode
+    z.i2N = iN + 2 * z.ipad
+    z.i3N = z.i2N + z.p3N - 1                                             # "full" convolution
+    i4N = iN if keep_size else iN + z.p3N - 1
     i4s = (i4N - 1) * ip
-    ext = np.asarray(img.extent, dtype=np.float64) + np.asarray(psfs[0].extent, dtype=np.float64)
+    ext = np.asarray(img.extent, dtype=np.float64) + np.asarray(psf0.extent, dtype=np.float64)
     xm, ym = (ext[0] + ext[1]) / 2, (ext[2] + ext[3]) / 2
-    i4e = [xm - i4s[0] / 2, xm + i4s[0] / 2, ym - i4s[1] / 2, ym + i4s[1] / 2]
+    z.i4e = [xm - i4s[0] / 2, xm + i4s[0] / 2, ym - i4s[1] / 2, ym + i4s[1] / 2]
+    return z
 
-    # ---- image planes on the device: pad for the mode, flip for m < 0 (convolve.py:342-371) -------------------
+
+def _image_planes(planes, z: _Sizes, custom_padding, padding_mode, pval_lin, m, dev) -> torch.Tensor:
+    """The image on the device, padded for the mode and flipped for m < 0 (convolve.py:342-371): (Ny, Nx) or (Ny, Nx, 3)."""
+    ipad = z.ipad
     if custom_padding:
         width = ((int(ipad[1]),) * 2, (int(ipad[0]),) * 2) + (((0, 0),) if planes.ndim == 3 else ())
         if padding_mode == "constant":
@@ -189,63 +176,42 @@ def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str 
             planes = np.pad(planes, width, mode=padding_mode)
     if m < 0:
         planes = planes[::-1, ::-1]
-    d_img = torch.from_numpy(np.ascontiguousarray(planes)).to(dev)
-    img_planes = [d_img] if d_img.ndim == 2 else [d_img[:, :, c] for c in range(3)]
-    if not img_color and not gray_only:
-        img_planes = img_planes * 3  # a grey image has three equal linear-sRGB channels
+    return torch.from_numpy(np.ascontiguousarray(planes)).to(dev)
 
-    # ---- PSF planes: linear sRGB, area resize, zero rim (convolve.py:228-250, 373-397) ------------------------
-    Wy = _area_weights(int(pN[1]), int(p2N[1]), dev)
-    Wx = _area_weights(int(pN[0]), int(p2N[0]), dev)
-    keep = float(pN[0] * pN[1]) / float(p2N[0] * p2N[1])  # an area average times this keeps the PSF's sum
-    t_x2r = torch.tensor(_XYZ_TO_RGBL, dtype=torch.float64, device=dev)
 
-    def psf_planes(p) -> list:
-        if isinstance(p, RenderImage):
-            p._check_for_image()
-            xyz = (p._dev if p._dev is not None else torch.from_numpy(p._data).to(dev))[:, :, :3]
-            lin = xyz.reshape(-1, 3) @ t_x2r.T  # color.xyz_to_srgb_linear(rendering_intent="Ignore", normalize=False)
-            chans = [lin[:, c].reshape(xyz.shape[0], xyz.shape[1]) for c in range(3)]
-        else:
-            g = torch.from_numpy(srgb_to_srgb_linear(p.data)).to(dev)
-            tot = g.sum()
-            if float(tot):
-                g = g * (1 / tot)
-            chans = [g]
-        out = []
-        for ch in chans:
-            small = (Wy @ ch @ Wx.T) * keep
-            out.append(torch.nn.functional.pad(small, (ppad, ppad, ppad, ppad)))
-        return out
+class _Resize:
+    """Area resize of a PSF plane to the image's pixel pitch, sum kept (convolve.py:373-397)."""
 
-    psf_sets = [psf_planes(p) for p in psfs]  # per PSF: one plane (grey) or three (R, G, B response)
+    def __init__(self, z: _Sizes, dev) -> None:
+        self.Wy = _area_weights(int(z.pN[1]), int(z.p2N[1]), dev)
+        self.Wx = _area_weights(int(z.pN[0]), int(z.p2N[0]), dev)
+        self.keep = float(z.pN[0] * z.pN[1]) / float(z.p2N[0] * z.p2N[1])  # an area average times this keeps the PSF's sum
 
-    # ---- convolution: real FFTs of every distinct plane, products, inverse transforms (convolve.py:400-437) ---
-    Ly, Lx = _fast_len(int(i3N[1])), _fast_len(int(i3N[0]))
-    f_img = [torch.fft.rfft2(pl, s=(Ly, Lx)) for pl in (img_planes if img_color or gray_only else img_planes[:1])]
-    if not img_color and not gray_only:
-        f_img = f_img * 3
-    f_psf = [[torch.fft.rfft2(pl, s=(Ly, Lx)) for pl in planes_] for planes_ in psf_sets]
+    def __call__(self, ch: torch.Tensor) -> torch.Tensor:
+        return (self.Wy @ ch @ self.Wx.T) * self.keep
 
-    def back(spec) -> torch.Tensor:
-        return torch.fft.irfft2(spec, s=(Ly, Lx))[:int(i3N[1]), :int(i3N[0])]
 
-    if gray_only:
-        res = back(f_img[0] * f_psf[0][0])                                            # (Ny, Nx)
-    elif three_psf:  # image channel i spreads into all three output channels through PSF i
-        res = torch.stack([back(sum(f_img[i] * f_psf[i][j] for i in range(3))) for j in range(3)], dim=2)
-    else:            # channel by channel (a grey PSF serves all three)
-        one = f_psf[0]
-        res = torch.stack([back(f_img[c] * one[c if len(one) == 3 else 0]) for c in range(3)], dim=2)
+def _gray_psf_plane(p, resize: _Resize, dev) -> torch.Tensor:
+    """A GrayscaleImage PSF in linear sRGB, normalised to sum 1, at the image's pitch (convolve.py:228-250); no rim."""
+    g = torch.from_numpy(srgb_to_srgb_linear(p.data)).to(dev)
+    tot = g.sum()
+    if float(tot):
+        g = g * (1 / tot)
+    return resize(g)
 
-    # ---- slicing (convolve.py:440-452) ------------------------------------------------------------------------
+
+def _slice(res: torch.Tensor, z: _Sizes, custom_padding, keep_size) -> torch.Tensor:
+    """Removes the padding rim and, for keep_size, crops to the input's pixel count (convolve.py:440-452)."""
     if custom_padding:
-        res = res[ipad[1]:res.shape[0] - ipad[1], ipad[0]:res.shape[1] - ipad[0]]
+        res = res[z.ipad[1]:res.shape[0] - z.ipad[1], z.ipad[0]:res.shape[1] - z.ipad[0]]
     if keep_size:
-        off = (i3N - i2N) // 2
-        res = res[off[1]:off[1] + iN[1], off[0]:off[0] + iN[0]]
+        off = (z.i3N - z.i2N) // 2
+        res = res[off[1]:off[1] + z.iN[1], off[0]:off[0] + z.iN[0]]
+    return res
 
-    # ---- back to sRGB ------------------------------------------------------------------------------------------
+
+def _to_srgb(res: torch.Tensor, gray_only: bool, cargs: dict, i4e, dev):
+    """Linear sRGB (Ny, Nx) or (Ny, Nx, 3) -> GrayscaleImage / RGBImage through the final colour mapping."""
     if gray_only:
         if cargs.get("normalize", True):
             mx = float(res.max())
@@ -257,6 +223,7 @@ def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str 
     opts = dict(rendering_intent="Absolute", normalize=True, clip=True, L_th=0, chroma_scale=None) | cargs
     ny, nx = int(res.shape[0]), int(res.shape[1])
     t_r2x = torch.tensor(_RGBL_TO_XYZ, dtype=torch.float64, device=dev)
+    t_x2r = torch.tensor(_XYZ_TO_RGBL, dtype=torch.float64, device=dev)
     xyz = res.reshape(-1, 3) @ t_r2x.T
     intent = opts["rendering_intent"]
     if intent == "Ignore":  # plain matrix conversion, out-of-gamut values only clipped (srgb.py:318-319 path)
@@ -285,3 +252,167 @@ def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str 
     _capi.check(lib.ot_image_convert(ptr(hist), nx, ny, 1, mode, 1.0, 683.0, float(opts["L_th"]), cs, ptr(out), ptr(ws),
                                      stream_ptr()))
     return RGBImage(out.cpu().numpy().reshape(ny, nx, 3), extent=i4e)
+
+
+_SAME_SIZE = "All PSF sizes need to be the same. Render the detector image with the same manual extent option."
+
+
+def convolve(img, psf, m: float = 1, keep_size: bool = False, padding_mode: str = "constant", padding_value=None,
+             cargs: dict = {}):
+    """Convolve an image with a point spread function (same signature, cases and errors as the reference's).
+
+    1. GrayscaleImage with a GrayscaleImage PSF -> GrayscaleImage
+    2. GrayscaleImage with a RenderImage PSF (colour information in the PSF) -> RGBImage
+    3. RGBImage with a GrayscaleImage PSF -> RGBImage
+    4. RGBImage with a list of three RenderImage PSFs, rendered for the sRGB R, G, B primaries -> RGBImage
+
+    `m` scales the image before the convolution (|m| > 1 enlarges, m < 0 flips it).  `padding_mode` is one of
+    numpy.pad's modes, `padding_value` (three values for an RGBImage, one otherwise) belongs to "constant".
+    `keep_size` crops the result back to the pixel count of the input.  `cargs` overrides the arguments of the final
+    colour mapping, by default rendering_intent="Absolute", normalize=True, clip=True, L_th=0, chroma_scale=None.
+    """
+    _check_arguments(img, m, keep_size, cargs)
+    img_color = isinstance(img, RGBImage)
+    gray_only = isinstance(psf, GrayscaleImage) and not img_color  # one plane in, one plane out
+    three_psf = isinstance(psf, list) and len(psf) == 3
+    psf_color = isinstance(psf, RenderImage) or three_psf
+    dev = require_device()
+    planes, pval_lin, custom_padding = _image_input(img, padding_mode, padding_value)
+
+    # ---- PSF checks (convolve.py:206-253) ----------------------------------------------------------------------
+    if psf_color:
+        psfs = psf if three_psf else [psf]
+        if img_color and not three_psf:
+            raise TypeError("A list of a R, G, B RenderImage PSF is required for convolving"
+                            " a colored image with a colored PSF.")
+        if not img_color and three_psf:
+            raise TypeError("A single colored RenderImage is sufficient for a grayscale image.")
+        for i, p_i in enumerate(psfs):
+            check_type(f"psf[{i}]", p_i, RenderImage)
+            if not np.all(np.asarray(psfs[0].extent) == np.asarray(p_i.extent)):
+                raise ValueError(_SAME_SIZE)
+    else:
+        check_type("psf", psf, GrayscaleImage)
+        psfs = [psf]
+
+    z = _sizes(img, psfs[0], m, keep_size, custom_padding)
+    i3N, ppad = z.i3N, z.ppad
+    d_img = _image_planes(planes, z, custom_padding, padding_mode, pval_lin, m, dev)
+    img_planes = [d_img] if d_img.ndim == 2 else [d_img[:, :, c] for c in range(3)]
+    if not img_color and not gray_only:
+        img_planes = img_planes * 3  # a grey image has three equal linear-sRGB channels
+
+    # ---- PSF planes: linear sRGB, area resize, zero rim (convolve.py:228-250, 373-397) ------------------------
+    resize = _Resize(z, dev)
+    t_x2r = torch.tensor(_XYZ_TO_RGBL, dtype=torch.float64, device=dev)
+
+    def psf_planes(p) -> list:
+        if isinstance(p, RenderImage):
+            p._check_for_image()
+            xyz = (p._dev if p._dev is not None else torch.from_numpy(p._data).to(dev))[:, :, :3]
+            lin = xyz.reshape(-1, 3) @ t_x2r.T  # color.xyz_to_srgb_linear(rendering_intent="Ignore", normalize=False)
+            small = [resize(lin[:, c].reshape(xyz.shape[0], xyz.shape[1])) for c in range(3)]
+        else:
+            small = [_gray_psf_plane(p, resize, dev)]
+        return [torch.nn.functional.pad(pl, (ppad, ppad, ppad, ppad)) for pl in small]
+
+    psf_sets = [psf_planes(p) for p in psfs]  # per PSF: one plane (grey) or three (R, G, B response)
+
+    # ---- convolution: real FFTs of every distinct plane, products, inverse transforms (convolve.py:400-437) ---
+    Ly, Lx = _fast_len(int(i3N[1])), _fast_len(int(i3N[0]))
+    f_img = [torch.fft.rfft2(pl, s=(Ly, Lx)) for pl in (img_planes if img_color or gray_only else img_planes[:1])]
+    if not img_color and not gray_only:
+        f_img = f_img * 3
+    f_psf = [[torch.fft.rfft2(pl, s=(Ly, Lx)) for pl in planes_] for planes_ in psf_sets]
+
+    def back(spec) -> torch.Tensor:
+        return torch.fft.irfft2(spec, s=(Ly, Lx))[:int(i3N[1]), :int(i3N[0])]
+
+    if gray_only:
+        res = back(f_img[0] * f_psf[0][0])                                            # (Ny, Nx)
+    elif three_psf:  # image channel i spreads into all three output channels through PSF i
+        res = torch.stack([back(sum(f_img[i] * f_psf[i][j] for i in range(3))) for j in range(3)], dim=2)
+    else:            # channel by channel (a grey PSF serves all three)
+        one = f_psf[0]
+        res = torch.stack([back(f_img[c] * one[c if len(one) == 3 else 0]) for c in range(3)], dim=2)
+
+    return _to_srgb(_slice(res, z, custom_padding, keep_size), gray_only, cargs, z.i4e, dev)
+
+
+def _psf_grid(psfs):
+    """The nodes of `convolve_field` as rows of GrayscaleImages of one shape and extent."""
+    from .psf import HuygensPSF, HuygensStack
+    if isinstance(psfs, (GrayscaleImage, RenderImage, HuygensPSF, HuygensStack, str)) or not hasattr(psfs, "__len__"):
+        raise TypeError("psfs must be a nested sequence [Gy][Gx] of point spread functions; a single one is [[psf]].")
+    if len(psfs) == 0:
+        raise ValueError("psfs is empty.")
+    grid = []
+    for b, row in enumerate(psfs):
+        if isinstance(row, (GrayscaleImage, RenderImage, HuygensPSF, HuygensStack, str)) or not hasattr(row, "__len__"):
+            raise TypeError("psfs must be a nested sequence [Gy][Gx] of point spread functions; a single one is [[psf]].")
+        if len(row) == 0 or len(row) != len(psfs[0]):
+            raise ValueError(f"psfs must be a rectangular, non-empty grid: row {b} has {len(row)} nodes, "
+                             f"row 0 has {len(psfs[0])}.")
+        out = []
+        for a, p in enumerate(row):
+            if isinstance(p, RenderImage) or (isinstance(p, (list, tuple)) and len(p) == 3):
+                raise TypeError("Colour PSFs (a RenderImage, or a list of three) are not supported by convolve_field.")
+            if isinstance(p, HuygensPSF):
+                p = p.to_image()
+            check_type(f"psfs[{b}][{a}]", p, GrayscaleImage)
+            out.append(p)
+        grid.append(out)
+    p0 = grid[0][0]
+    for row in grid:
+        for p in row:
+            if tuple(p.shape) != tuple(p0.shape) or not np.all(np.asarray(p0.extent) == np.asarray(p.extent)):
+                raise ValueError(_SAME_SIZE)
+    return grid
+
+
+def convolve_field(img, psfs, m: float = 1, keep_size: bool = False, padding_mode: str = "constant", padding_value=None,
+                   node_weights=None, cargs: dict = {}):
+    """Convolve an image with a point spread function that varies over the field ("Field-dependent convolution").
+
+    `psfs` is a nested sequence [Gy][Gx] of GrayscaleImage or HuygensPSF (taken through `to_image()`), all of one shape and
+    extent; `[[psf]]` is `convolve(img, psf)`.  Node [b][a] belongs to the row fraction b / (Gy - 1) and the column fraction
+    a / (Gx - 1) of the result, [0][0] the lower left as in every image; for m < 0 that is after the flip.  Every source pixel is
+    spread by the bilinear blend of the PSFs of the four nodes around it.  Each PSF is normalised to sum 1, as in `convolve`;
+    `node_weights`, a (Gy, Gx) array of finite non-negative numbers, not all zero, scales them: the relative illumination of the
+    field points.  `m`, `keep_size`, `padding_mode`, `padding_value` and `cargs` as for `convolve`; a GrayscaleImage gives a
+    GrayscaleImage, an RGBImage an RGBImage, with convolve's shape and extent.  The sum is formed directly on the device
+    (`ot_convolve_field`, csrc/ot_convolve.hpp): no FFT.
+    """
+    _check_arguments(img, m, keep_size, cargs)
+    grid = _psf_grid(psfs)
+    Gy, Gx = len(grid), len(grid[0])
+    if node_weights is None:
+        nw = np.ones((Gy, Gx))
+    else:
+        nw = np.asarray(node_weights, dtype=np.float64)
+        if nw.shape != (Gy, Gx):
+            raise ValueError(f"node_weights must have the shape of the grid {(Gy, Gx)}, but has shape {nw.shape}.")
+        if not np.all(np.isfinite(nw)) or np.any(nw < 0) or not np.any(nw > 0):
+            raise ValueError("node_weights must be finite, non-negative and not all zero.")
+    if max(Gy, Gx) > _capi.CONVF_MAX_GRID:
+        raise ValueError(f"A grid of {Gy} x {Gx} PSFs is above the limit of {_capi.CONVF_MAX_GRID} nodes per axis.")
+    planes, pval_lin, custom_padding = _image_input(img, padding_mode, padding_value)
+    z = _sizes(img, grid[0][0], m, keep_size, custom_padding)
+    if max(z.p2N) > _capi.CONVF_MAX_PSF:
+        raise ValueError(f"The PSF has {int(z.p2N[1])} x {int(z.p2N[0])} pixels at the image's pixel pitch, above the limit of "
+                         f"{_capi.CONVF_MAX_PSF} per axis: use a smaller PSF extent or a coarser image.")
+    dev = require_device()
+
+    d_img = _image_planes(planes, z, custom_padding, padding_mode, pval_lin, m, dev)
+    d_img = (d_img[None] if d_img.ndim == 2 else d_img.permute(2, 0, 1)).contiguous()      # planar (n_ch, Ny, Nx)
+    resize = _Resize(z, dev)
+    d_psf = torch.stack([torch.stack([_gray_psf_plane(p, resize, dev) for p in row]) for row in grid])
+    d_psf = (d_psf * torch.from_numpy(nw).to(dev)[:, :, None, None]).contiguous()          # (Gy, Gx, py, px)
+    n_ch, ny, nx = (int(v) for v in d_img.shape)
+    py, px = int(z.p2N[1]), int(z.p2N[0])
+    out = torch.empty(n_ch, ny + py - 1, nx + px - 1, dtype=torch.float64, device=dev)
+    _capi.check(_capi.load_library().ot_convolve_field(ptr(d_img), n_ch, ny, nx, int(z.ipad[1]), int(z.ipad[0]), int(z.iN[1]),
+                                                       int(z.iN[0]), ptr(d_psf), Gy, Gx, py, px, ptr(out), stream_ptr()))
+    res = torch.nn.functional.pad(out, (z.ppad,) * 4)   # the PSF's zero rim of convolve, which only shifts the result
+    res = res[0] if n_ch == 1 else res.permute(1, 2, 0)
+    return _to_srgb(_slice(res, z, custom_padding, keep_size), n_ch == 1, cargs, z.i4e, dev)
