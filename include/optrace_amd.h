@@ -771,6 +771,38 @@ int ot_wavefront_map(int64_t n, const double* u, const double* v, const double* 
 int ot_wavefront_zernike(int64_t n, const double* u, const double* v, const double* opl, const float* w, const double* moments,
                          double pupil_radius, int32_t J, double* workspace, double* out, void* stream);
 
+/* ---- beam footprints (Raytracer.footprints; no counterpart in optrace) ------------------------------------------
+ * Per section i of the storage (0: the sources; 1 .. nt - 2: behind tracing surface i - 1; nt - 1: the rays' ends), over the
+ * rays [first, first + count): the living rays T = {w[i] > 0}, the arriving rays A = {w[i - 1] > 0} (A = T in section 0) and
+ * where the living ones cross the surface.  Reads p and w only; positions and weights of rays outside T and A are not read into
+ * arithmetic.  All arithmetic in f64.  Pointers are DEVICE; launches are ordered on `stream` and nothing is waited for.  A null
+ * argument, a ray range outside the storage, nt < 2: OT_ERR_INVALID; n_px outside 1 .. OT_FP_MAX_PX, nt above
+ * OT_FP_MAX_SECTIONS: OT_ERR_UNSUPPORTED, both before a device is looked for; count = 0 returns OT_OK without a launch and
+ * leaves the outputs alone.
+ * ot_footprint_moments: records[nt * OT_FP_M], per section
+ *    0 sum_T w        1 |T|            2 sum_A w[i - 1]   3 |A|
+ *    4 sum_T w x      5 sum_T w y      6 sum_T w z
+ *    7 min x  8 max x  9 min y  10 max y  11 min z  12 max z   over T; NaN when T is empty
+ *   13 sum_T w dx^2  14 sum_T w dy^2  15 sum_T w dx dy          d = (x, y) - c, c = (slot 4, slot 5) / slot 0, formed before
+ *                                                               squaring: a second pass over the planes
+ *   16 max_T ((x - ax)^2 + (y - ay)^2)                          (ax, ay) = axis[2 i], axis[2 i + 1]; 0 when T is empty
+ *   axis[2 * nt]: the xy of the source (section 0) and of the surfaces; finite.  workspace >= ot_footprint_workspace(count, nt)
+ *   doubles (0 for arguments out of range).  All sections go in one launch per pass; the sums are added in an order fixed by
+ *   count alone: the same call returns the same bits, and slots 2, 3 of section i are bit for bit slots 0, 1 of section i - 1.
+ * ot_footprint_maps: maps[nt * n_px * n_px] (accumulated into: zero it first), section i += w of every ray of T in cell
+ *   row * n_px + column, column = min(floor(((x - ax) + R) / (2 R) * n_px), n_px - 1), not below 0, R = sqrt(slot 16) of
+ *   records (as ot_footprint_moments left them); row likewise from y; cell 0 when R = 0.  The one call whose sums depend on
+ *   the order of arrival (f64 atomics). */
+#define OT_FP_M 17
+#define OT_FP_MAX_PX 1024
+#define OT_FP_MAX_SECTIONS 65535
+#define OT_FP_BLOCKS 1024 /* most workgroups per section and 2^28 rays whose partial sums the workspace holds */
+int64_t ot_footprint_workspace(int64_t count, int32_t nt);
+int ot_footprint_moments(const ot_rays* rays, int64_t first, int64_t count, const double* axis, double* workspace, double* records,
+                         void* stream);
+int ot_footprint_maps(const ot_rays* rays, int64_t first, int64_t count, const double* axis, const double* records, int32_t n_px,
+                      double* maps, void* stream);
+
 /* ---- Huygens point spread function (Raytracer.huygens_psf; no counterpart in optrace) -----------------------------
  * The coherent sum of one spherical wavelet per ray over the points of an image plane, from the rays' places and optical
  * paths on the reference sphere of the wavefront analysis above.  Pointers are DEVICE unless said otherwise; launches are

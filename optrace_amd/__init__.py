@@ -20,6 +20,7 @@ from .render_image import RenderImage
 from .spot import SpotAnalysis
 from .wavefront import WavefrontAnalysis
 from .psf import HuygensPSF, HuygensStack
+from .footprint import Footprints
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
 from .convolve import convolve, convolve_field

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(OT_RED_THREADS) void spot_first_kernel(int64_t n, c
         v[2] += wd * y[i];
         v[3] += 1.0;  // (exact up to 2^53 hits)
     });
-    block_reduce_fixed<4, -1>(v, part + 4 * (int64_t)blockIdx.x);
+    block_reduce_fixed<4, red_max()>(v, part + 4 * (int64_t)blockIdx.x);
 }
 
 // the centroid every later pass subtracts: the same two IEEE quotients as the host forms from the record
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(OT_RED_THREADS) void spot_central_kernel(int64_t n,
         v[2] += wd * (dx * dy);
         v[3] = fmax(v[3], dx * dx + dy * dy);
     });
-    block_reduce_fixed<4, 3>(v, part + 4 * (int64_t)blockIdx.x);
+    block_reduce_fixed<4, red_max(3)>(v, part + 4 * (int64_t)blockIdx.x);
 }
 
 // pass 3: hist[n_radii] += w.  LDS-privatised when the bins fit (lds_bins > 0), otherwise global atomics.
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(OT_RED_THREADS, 4) void spot_otf_kernel(int64_t n, 
             v[3 * OT_SPOT_CHUNK + j] -= wd * sn;
         }
     });
-    block_reduce_fixed<4 * OT_SPOT_CHUNK, -1>(v, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * (4 * OT_SPOT_CHUNK));
+    block_reduce_fixed<4 * OT_SPOT_CHUNK, red_max()>(v, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * (4 * OT_SPOT_CHUNK));
 }
 
 // part[nblocks][chunks][4][8] -> out[4][K]: thread (q, k) adds its partials in index order

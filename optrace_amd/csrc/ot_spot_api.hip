@@ -10,9 +10,9 @@ extern "C" int ot_spot_moments(int64_t n, const uint32_t* fill, const double* x,
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = reduce_blocks(n, OT_SPOT_BLOCKS);
     hipLaunchKernelGGL(spot_first_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, x, y, w, fill, workspace);
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 4, 0u, 0u, moments);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 4, 0u, 0u, moments, 0, 0);
     hipLaunchKernelGGL(spot_central_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, x, y, w, fill, moments, workspace);
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 4, 1u << 3, 0u, moments + 4);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 4, 1u << 3, 0u, moments + 4, 0, 0);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(OT_RED_THREADS) void wf_focus_kernel(ot_rays R, int
         v[WFF_B + 1] += w * (py - s.y * sp);
         v[WFF_B + 2] += w * (pz - s.z * sp);
     });
-    block_reduce_fixed<WFF_M, -1>(v, part + WFF_M * (int64_t)blockIdx.x);
+    block_reduce_fixed<WFF_M, red_max()>(v, part + WFF_M * (int64_t)blockIdx.x);
 }
 
 // The hot pass, one thread per ray of [first, first + count): (k + 2) positions and (k + 1) indices read plane by plane
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(OT_RED_THREADS) void wf_first_kernel(int64_t n, con
         a[WF_OPL_MIN] = fmax(a[WF_OPL_MIN], -l);
         a[WF_OPL_MAX] = fmax(a[WF_OPL_MAX], l);
     });
-    block_reduce_fixed<8, WF_OPL_MIN, WF_OPL_MAX>(a, part + 8 * (int64_t)blockIdx.x);
+    block_reduce_fixed<8, red_max(WF_OPL_MIN, WF_OPL_MAX)>(a, part + 8 * (int64_t)blockIdx.x);
 }
 
 // part[gridDim.x][2]: sum w opd^2 | max (du^2 + dv^2)
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(OT_RED_THREADS) void wf_central_kernel(int64_t n, c
         a[0] += (double)wi * (d * d);
         a[1] = fmax(a[1], du * du + dv * dv);
     });
-    block_reduce_fixed<2, 1>(a, part + 2 * (int64_t)blockIdx.x);
+    block_reduce_fixed<2, red_max(1)>(a, part + 2 * (int64_t)blockIdx.x);
 }
 
 // The pupil radius the later passes divide by when the caller gives none, stored so that the host reports this very number
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(OT_RED_THREADS) void wf_zernike_kernel(int64_t n, c
         acc[JT + 1] += wa * opd;
         acc[JT + 2] += wb * opd;
     }
-    block_reduce_fixed<S, -1>(acc, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * S);
+    block_reduce_fixed<S, red_max()>(acc, part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * S);
 }
 
 // part[nblocks][chunks][JT + 3] -> out: G's upper triangle row by row (i <= j < J), then g[J].  One thread per slot of a chunk

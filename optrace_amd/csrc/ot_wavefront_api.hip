@@ -16,7 +16,7 @@ extern "C" int ot_wavefront_focus(const ot_rays* rays, int64_t first, int64_t co
     const unsigned blocks = reduce_blocks(count, OT_WF_BLOCKS);
     hipLaunchKernelGGL(wf_focus_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, *rays, first, count, (int)section, origin[0], origin[1],
                        origin[2], workspace);
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, (int)WFF_M, 0u, 0u, sums);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, (int)WFF_M, 0u, 0u, sums, 0, 0);
     HIP_TRY(hipGetLastError());
     return OT_OK;
 }
@@ -45,9 +45,9 @@ extern "C" int ot_wavefront_moments(int64_t n, const double* u, const double* v,
     const unsigned blocks = reduce_blocks(n, OT_WF_BLOCKS);
     const unsigned maxima = (1u << WF_OPL_MIN) | (1u << WF_OPL_MAX);
     hipLaunchKernelGGL(wf_first_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, u, v, opl, w, wl, workspace);
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 8, maxima, 1u << WF_OPL_MIN, moments);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 8, maxima, 1u << WF_OPL_MIN, moments, 0, 0);
     hipLaunchKernelGGL(wf_central_kernel, dim3(blocks), dim3(OT_RED_THREADS), 0, st, n, u, v, opl, w, moments, workspace);
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 2, 2u, 0u, moments + WF_WOPD2);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(OT_RED_THREADS), 0, st, workspace, (int)blocks, 2, 2u, 0u, moments + WF_WOPD2, 0, 0);
     hipLaunchKernelGGL(wf_pupil_radius_kernel, dim3(1), dim3(1), 0, st, moments);
     HIP_TRY(hipGetLastError());
     return OT_OK;

@@ -37,6 +37,8 @@ from . import wavefront as _wavefront
 from .wavefront import WavefrontAnalysis
 from . import psf as _psf
 from .psf import HuygensPSF, HuygensStack
+from . import footprint as _footprint
+from .footprint import Footprints
 from .geometry.ray_source import RaySource
 from .scene import CompiledScene, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
@@ -850,6 +852,34 @@ class Raytracer(Group):
         Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the point spread function holds")
         return _psf.analyse_stack(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_px, size, dz, bands,
                                   long_desc=f"Huygens PSF stack of {label} behind section {k}")
+
+    def footprints(self, source_index: int = None, n_px: int = None) -> Footprints:
+        """Beam footprint and power budget at every surface, of one source's rays or of all (None), no counterpart in optrace:
+        per section of the stored trace the rays alive and arriving with their power, and centroid, extent, RMS size and largest
+        distance from the surface's axis of where the living rays cross the surface, reduced on the GPU from the position and
+        weight planes (footprint.py).  n_px: cells per side of a power map of every footprint (`Footprints.image`), 1 to 1024;
+        None: no maps."""
+        _footprint.check_arguments(source_index, n_px)
+        require_device()  # (said before anything about the rays: without a device there are none)
+        if not self.ray_sources:
+            raise RuntimeError("Ray Sources Missing.")
+        self._need_rays()
+        Ns, Ne = self._ray_range(source_index)
+        self._need_current()
+        surfaces = self.tracing_surfaces
+        labels = ["sources" if source_index is None else f"{RaySource.abbr}{source_index}"]
+        for el in self.elements:
+            if isinstance(el, (Lens, Filter, Aperture)):
+                group = self.lenses if isinstance(el, Lens) else self.filters if isinstance(el, Filter) else self.apertures
+                tag = f"{el.abbr}{next(k for k, other in enumerate(group) if other is el)}"
+                two = el.back is not None and not getattr(el, "is_ideal", False)  # (as `tracing_surfaces` counts them)
+                labels += [f"{tag} front", f"{tag} back"] if two else [tag]
+        labels.append("end")
+        # the last section is empty (every ray ends absorbed): any finite pair serves as its axis
+        axis = [self.ray_sources[source_index or 0].pos[:2]] + [surf.pos[:2] for surf in surfaces] + [[0.0, 0.0]]
+        radii = [np.nan] + [_footprint.surface_radius(surf) for surf in surfaces] + [np.nan]
+        who = "all rays" if source_index is None else f"{RaySource.abbr}{source_index}"
+        return _footprint.analyse(self.rays, Ns, Ne - Ns, axis, n_px, labels, radii, long_desc=f"Footprints of {who}")
 
     def _section_bundle(self, source_index, section, holds: str):
         """What the analyses of a stored section share, after their own argument checks: the device, current rays, the ray range
