@@ -315,6 +315,14 @@ class LineMarker(_Marker):
         self._new_lock = True
 
 
+def section_sides(el) -> tuple:
+    """(side, surface) of the surfaces of an element that end a ray section: ("front", ..), ("back", ..), or ("", ..) for the
+    only one of a single-surface element and of an ideal lens (its back is its front).  The one place that counts them."""
+    if el.back is None or getattr(el, "is_ideal", False):
+        return (("", el.front),)
+    return ("front", el.front), ("back", el.back)
+
+
 class Group(BaseClass):
     """Container of elements with an ambient index n0 (group.py:18-308)."""
 
@@ -353,14 +361,7 @@ class Group(BaseClass):
     def tracing_surfaces(self) -> list:
         """Front/back surfaces of lenses, filters and apertures in z order (group.py:84-98); an ideal lens counts
         once."""
-        out = []
-        for el in self.elements:
-            if not isinstance(el, (Lens, Filter, Aperture)):
-                continue
-            out.append(el.front)
-            if el.back is not None and not getattr(el, "is_ideal", False):
-                out.append(el.back)
-        return out
+        return [surf for el in self.elements if isinstance(el, (Lens, Filter, Aperture)) for _, surf in section_sides(el)]
 
     @property
     def extent(self) -> tuple:

@@ -24,7 +24,7 @@ import torch
 from . import _capi
 from . import base as _base
 from .base import check_type
-from .geometry.elements import Group, Aperture, Detector, Lens, Filter
+from .geometry.elements import Group, Detector
 from .geometry.surfaces import Surface, Point, Line, SphericalSurface, RingSurface, SlitSurface
 from .options import global_options
 from .ray_storage import RayStorage, TailStorage, SceneRef
@@ -40,7 +40,7 @@ from .psf import HuygensPSF, HuygensStack
 from . import footprint as _footprint
 from .footprint import Footprints
 from .geometry.ray_source import RaySource
-from .scene import CompiledScene, tracing_elements
+from .scene import CompiledScene, SectionTable, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
 from ._warn import warning
 from . import detector as _detector
@@ -216,29 +216,15 @@ class Raytracer(Group):
         "HURB_NEG_DIR": "have negative z-direction after ray bending at surface {s} ({n}), set to absorbed.",
     }
 
-    def _surface_names(self) -> list:
-        """Names of the ray sections in tracing order: the source, every tracing surface by z, the outline."""
-        labelled = []
-        for kind, group in (("Lens", self.lenses), ("Aperture", self.apertures), ("Filter", self.filters)):
-            for k, el in enumerate(group):
-                tag = f"{kind} {el.abbr}{k}"
-                if el.has_back():
-                    labelled += [(el.front.pos[2], f"front surface of {tag}"), (el.back.pos[2], f"back surface of {tag}")]
-                else:
-                    labelled.append((el.pos[2], f"surface of {tag}"))
-        labelled.sort(key=lambda item: item[0])
-        return ["RaySource"] + [name for _, name in labelled] + ["Outline"]
-
     def _show_messages(self, N) -> None:
         """One warning per non-zero event counter (raytracer.py:207-244)."""
         if not global_options.show_warnings or not self._msgs.any():
             return
-        names = self._surface_names()
+        names = SectionTable(self).names()
         for kind, sec in zip(*np.nonzero(self._msgs)):
             count = self._msgs[kind, sec]
-            where = names[sec] if sec < len(names) else "?"
             warning(f"{count} rays ({100*count/N:.3g}% of all rays) "
-                    + self._EVENT_TEXT[self.INFOS(kind).name].format(s=sec, n=where))
+                    + self._EVENT_TEXT[self.INFOS(kind).name].format(s=sec, n=names[sec]))
 
     # ---- geometry checks (raytracer.py:510-664) ---------------------------------------------------------
     def _pretrace_check(self, N: int, key: str) -> bool:
@@ -485,6 +471,19 @@ class Raytracer(Group):
         if not 0 <= source_index < len(self.ray_sources):
             raise IndexError("Invalid source_index.")
         return int(self.rays.B_list[source_index]), int(self.rays.B_list[source_index + 1])
+
+    def _stored_range(self, source_index) -> tuple:
+        """`_ray_range` for what reads the stored rays of a source: there are sources, rays, and they are current."""
+        if not self.ray_sources:
+            raise RuntimeError("Ray Sources Missing.")
+        self._need_rays()
+        Ns, Ne = self._ray_range(source_index)
+        self._need_current()
+        return Ns, Ne
+
+    @staticmethod
+    def _rays_tag(source_index) -> str:
+        return "all rays" if source_index is None else f"{RaySource.abbr}{source_index}"
 
     def _warn_ill(self, ill_count: int, detector_index: int) -> None:
         if ill_count:
@@ -819,9 +818,9 @@ class Raytracer(Group):
         surface; focus, radius: centre and signed radius of the sphere, default the point closest to all ray lines and its
         distance from the mean start of the section; n_zernike: Noll polynomials fitted; n_grid: cells per side of the map;
         pupil_radius: radius of the unit disc in units of |radius|, default the largest distance from the pupil centre."""
-        nt = len(self.tracing_surfaces) + 2
-        focus, radius, pupil_radius = _wavefront.check_arguments(nt, section, focus, radius, n_zernike, n_grid, pupil_radius)
-        Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the wavefront figures hold")
+        table = SectionTable(self)
+        focus, radius, pupil_radius = _wavefront.check_arguments(table.nt, section, focus, radius, n_zernike, n_grid, pupil_radius)
+        Ns, Ne, k, origin, label = self._section_bundle(table, source_index, section, "the wavefront figures hold")
         return _wavefront.analyse(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_zernike, n_grid, pupil_radius,
                                   long_desc=f"Wavefront of {label} behind section {k}")
 
@@ -833,9 +832,9 @@ class Raytracer(Group):
         points per side; size: side length of the square of image points about the focus in the plane z = focus z + dz, default
         ten mean wavelengths over the pupil radius (about eight Airy diameters in air).  For a source of several wavelengths or
         several planes: `huygens_stack`."""
-        nt = len(self.tracing_surfaces) + 2
-        focus, radius, size, dz = _psf.check_arguments(nt, section, focus, radius, n_px, size, dz)
-        Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the point spread function holds")
+        table = SectionTable(self)
+        focus, radius, size, dz = _psf.check_arguments(table.nt, section, focus, radius, n_px, size, dz)
+        Ns, Ne, k, origin, label = self._section_bundle(table, source_index, section, "the point spread function holds")
         return _psf.analyse(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_px, size, dz,
                             long_desc=f"Huygens PSF of {label} behind section {k}")
 
@@ -847,9 +846,9 @@ class Raytracer(Group):
         own (32 at the most); an int K, that many equal bands over the used rays' wavelengths; or K + 1 ascending edges in nm,
         the last band closed above.  The other arguments as for `huygens_psf`.  The result also gives the diffraction MTF
         (`HuygensStack.mtf`)."""
-        nt = len(self.tracing_surfaces) + 2
-        focus, radius, size, dz, bands = _psf.check_stack_arguments(nt, section, focus, radius, n_px, size, dz, bands)
-        Ns, Ne, k, origin, label = self._section_bundle(source_index, section, "the point spread function holds")
+        table = SectionTable(self)
+        focus, radius, size, dz, bands = _psf.check_stack_arguments(table.nt, section, focus, radius, n_px, size, dz, bands)
+        Ns, Ne, k, origin, label = self._section_bundle(table, source_index, section, "the point spread function holds")
         return _psf.analyse_stack(self.rays, Ns, Ne - Ns, k, origin, focus, radius, n_px, size, dz, bands,
                                   long_desc=f"Huygens PSF stack of {label} behind section {k}")
 
@@ -861,62 +860,30 @@ class Raytracer(Group):
         None: no maps."""
         _footprint.check_arguments(source_index, n_px)
         require_device()  # (said before anything about the rays: without a device there are none)
-        if not self.ray_sources:
-            raise RuntimeError("Ray Sources Missing.")
-        self._need_rays()
-        Ns, Ne = self._ray_range(source_index)
-        self._need_current()
-        surfaces = self.tracing_surfaces
-        labels = ["sources" if source_index is None else f"{RaySource.abbr}{source_index}"]
-        for el in self.elements:
-            if isinstance(el, (Lens, Filter, Aperture)):
-                group = self.lenses if isinstance(el, Lens) else self.filters if isinstance(el, Filter) else self.apertures
-                tag = f"{el.abbr}{next(k for k, other in enumerate(group) if other is el)}"
-                two = el.back is not None and not getattr(el, "is_ideal", False)  # (as `tracing_surfaces` counts them)
-                labels += [f"{tag} front", f"{tag} back"] if two else [tag]
-        labels.append("end")
-        # the last section is empty (every ray ends absorbed): any finite pair serves as its axis
-        axis = [self.ray_sources[source_index or 0].pos[:2]] + [surf.pos[:2] for surf in surfaces] + [[0.0, 0.0]]
-        radii = [np.nan] + [_footprint.surface_radius(surf) for surf in surfaces] + [np.nan]
-        who = "all rays" if source_index is None else f"{RaySource.abbr}{source_index}"
+        Ns, Ne = self._stored_range(source_index)
+        table, who = SectionTable(self), self._rays_tag(source_index)
+        axis, radii = table.axes_and_radii(source_index)
+        labels = table.labels("sources" if source_index is None else who)
         return _footprint.analyse(self.rays, Ns, Ne - Ns, axis, n_px, labels, radii, long_desc=f"Footprints of {who}")
 
-    def _section_bundle(self, source_index, section, holds: str):
-        """What the analyses of a stored section share, after their own argument checks: the device, current rays, the ray range
-        of the source, the section (default: the space behind the last surface), a point near its start and a label.  Warns of
-        an ideal lens before the section.  -> (Ns, Ne, k, origin, label)"""
-        surfaces = self.tracing_surfaces
-        nt = len(surfaces) + 2
+    def _section_bundle(self, table: SectionTable, source_index, section, holds: str):
+        """What the analyses of a stored section share, after their own argument checks against `table.nt`: the device, current
+        rays, the ray range of the source, the section (default: the space behind the last surface), a point near its start and a
+        label.  Warns of an ideal lens before the section.  -> (Ns, Ne, k, origin, label)"""
         if source_index is not None:
             check_type("source_index", source_index, int)
         require_device()  # (said before anything about the rays: without a device there are none)
-        if not self.ray_sources:
-            raise RuntimeError("Ray Sources Missing.")
-        self._need_rays()
-        Ns, Ne = self._ray_range(source_index)
-        self._need_current()
-        k = nt - 2 if section is None else section
-        # surface i of the geometry ends section i: those before section k are the surfaces 0 .. k - 1
-        i = 0
-        for el in self.elements:
-            if isinstance(el, (Lens, Filter, Aperture)):
-                if i < k and getattr(el, "is_ideal", False):
-                    warning(f"An ideal lens lies before section {k}: the optical path through an ideal lens is not defined, "
-                            f"{holds} up to what it would add.")
-                    break
-                i += 1 if el.back is None or getattr(el, "is_ideal", False) else 2
-        origin = surfaces[k - 1].pos if k else self.ray_sources[source_index or 0].pos
-        label = "all rays" if source_index is None else f"{RaySource.abbr}{source_index}"
-        return Ns, Ne, k, origin, label
+        Ns, Ne = self._stored_range(source_index)
+        k = table.nt - 2 if section is None else section
+        if table.ideal_before(k):
+            warning(f"An ideal lens lies before section {k}: the optical path through an ideal lens is not defined, "
+                    f"{holds} up to what it would add.")
+        return Ns, Ne, k, table.origin(k, source_index), self._rays_tag(source_index)
 
     # ---- source side (raytracer.py:1281-1352) ---------------------------------------------------------------
     def _hit_source(self, info: str, source_index: int = 0):
         """Section-0 device views of one source's rays: ((x, y), w, wl, extent)  (raytracer.py:1281-1309)."""
-        if not self.ray_sources:
-            raise RuntimeError("Ray Sources Missing.")
-        self._need_rays()
-        Ns, Ne = self._ray_range(int(source_index))
-        self._need_current()
+        Ns, Ne = self._stored_range(int(source_index))
         N, nt, d = self.rays._Np, self.rays.Nt, self.rays._dev  # (N: the plane stride of the storage)
         # element (ray r, section i, component c) of p lives at r + N * (i + nt * c); section 0 here
         xy = d["p"][Ns:Ne], d["p"][N * nt + Ns:N * nt + Ne]
@@ -973,13 +940,7 @@ class Raytracer(Group):
 
         # the search runs in the free gap around z_start: from the last surface (or source end) before it to the
         # first surface (or the outline's far face) behind it
-        gap = [self.N_EPS + max(rs.extent[5] for rs in self.ray_sources), self.outline[5] - self.N_EPS]
-        for surface in self.tracing_surfaces:
-            if surface.z_max > z_start:
-                gap[1] = surface.z_min
-                break
-            gap[0] = surface.z_max
-        bounds = [float(gap[0]), float(gap[1])]
+        bounds = SectionTable(self).gap(z_start, self.outline[5], self.N_EPS)
 
         Nt = 320  # cost function sampling points
         Ns, Ne = self._ray_range(source_index)
@@ -1075,7 +1036,7 @@ class Raytracer(Group):
         that is the ray's last section, which is all a render-only trace keeps."""
         if any(rs.orientation == "Function" for rs in self.ray_sources):  # (their generation needs a position pre-pass)
             return False
-        z_last = max([surf.z_max for surf in self.tracing_surfaces] + [rs.extent[5] for rs in self.ray_sources])
+        z_last = SectionTable(self).z_last()
         for k, p in zip(detector_index, pos):
             if not 0 <= k < len(self.detectors):  # (reported by the detector pass, after the trace like the reference)
                 return False
@@ -1147,7 +1108,7 @@ class Raytracer(Group):
         # (an extent is itself a list of numbers: only a list of extents counts as one)
         extentc = per_image(extent, "extent", isinstance(extent, list) and not isinstance(extent[0], (int, float)))
 
-        n_sec = len(self.tracing_surfaces) + 2
+        n_sec = SectionTable(self).nt
         if not self._scene_unchanged() and self._pretrace_check(min(N, 1000), self._geometry_key()):
             raise RuntimeError("Geometry checks failed. Tracing aborted. Check the warnings.")
         # Only the rays of the LAST chunk stay in the tracer (raytracer.py:1235-1267).  Every chunk before it is traced

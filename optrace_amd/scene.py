@@ -2,15 +2,20 @@
 
 The reference walks Python objects once per surface inside `Raytracer.trace` (raytracer.py:274, 307-397);
 here the walk happens once on the host and the device kernels only see `ot_scene_desc`.
+
+`SectionTable` is the way back: the ray sections of a trace (the source, one per tracing surface, the outline) against
+the elements of the scene, for everything that names, labels or measures a stored section.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from . import _capi
-from .geometry.elements import Lens, Filter, Aperture
+from .footprint import surface_radius
+from .geometry.elements import Lens, Filter, Aperture, section_sides
 from .geometry.surfaces import RectangularSurface, RingSurface, SlitSurface
 from .spectrum import LightSpectrum
 
@@ -20,7 +25,7 @@ class CompiledScene:
 
     def __init__(self, rt) -> None:
         self.elements_py = tracing_elements(rt)
-        self.nt = len(rt.tracing_surfaces) + 2
+        self.nt = SectionTable(rt).nt
 
         pool: list = []
         media: list = []
@@ -96,6 +101,62 @@ def tracing_elements(rt) -> list:
     end = Aperture(RectangularSurface(dim=[o[1] - o[0], o[3] - o[2]]),
                    pos=[(o[1] + o[0]) / 2, (o[2] + o[3]) / 2, o[5]])
     return [el for el in rt.elements if isinstance(el, (Lens, Filter, Aperture))] + [end]
+
+
+SectionRow = namedtuple("SectionRow", "element kind abbr index side surface ideal")
+# kind: "Lens", "Aperture", "Filter"; index: of the element within that list of its group; side: as `section_sides` gives it
+
+
+class SectionTable:
+    """The ray sections of a trace of a tracer (or of any Group, with the sources given) against its scene: section 0
+    starts at the source, row i - 1 is the surface that starts section i, the last section ends at the outline.  The rows
+    stand in the order of `Group.tracing_surfaces`, which is the order `CompiledScene` uploads.  Plain host objects, built
+    where they are asked for."""
+
+    def __init__(self, group, sources: list = None) -> None:
+        self.sources = list(group.ray_sources if sources is None else sources)
+        where = {id(el): (kind, k) for kind, els in (("Lens", group.lenses), ("Aperture", group.apertures),
+                                                      ("Filter", group.filters)) for k, el in enumerate(els)}
+        self.rows = [SectionRow(el, where[id(el)][0], el.abbr, where[id(el)][1], side, surf, getattr(el, "is_ideal", False))
+                     for el in group.elements if isinstance(el, (Lens, Filter, Aperture)) for side, surf in section_sides(el)]
+        self.surfaces = [row.surface for row in self.rows]  # (`group.tracing_surfaces`)
+        self.nt = len(self.rows) + 2
+
+    def names(self) -> list:
+        """Names of the nt sections by the surface they start at, as the warnings of a trace give them."""
+        return ["RaySource"] + [f"{r.side} surface of {r.kind} {r.abbr}{r.index}".lstrip() for r in self.rows] + ["Outline"]
+
+    def labels(self, first: str) -> list:
+        """Short labels of the nt sections (`Footprints.labels`); first: that of section 0."""
+        return [first] + [f"{r.abbr}{r.index} {r.side}".rstrip() for r in self.rows] + ["end"]
+
+    def ideal_before(self, k: int) -> bool:
+        """Is an ideal lens among the surfaces before section k, the surfaces 0 .. k - 1?"""
+        return any(row.ideal for row in self.rows[:k])
+
+    def origin(self, k: int, source_index: int = None):
+        """A point near the start of section k: the position of surface k - 1, of the source (None: the first) for k = 0."""
+        return self.surfaces[k - 1].pos if k else self.sources[source_index or 0].pos
+
+    def axes_and_radii(self, source_index: int = None) -> tuple:
+        """Per section the xy position its footprint refers to and the radius of its surface (NaN where there is none)."""
+        # the last section is empty (every ray ends absorbed): any finite pair serves as its axis
+        axis = [self.origin(0, source_index)[:2]] + [surf.pos[:2] for surf in self.surfaces] + [[0.0, 0.0]]
+        return axis, [np.nan] + [surface_radius(surf) for surf in self.surfaces] + [np.nan]
+
+    def z_last(self) -> float:
+        """z behind which nothing of the tracing geometry or of a source lies."""
+        return max([surf.z_max for surf in self.surfaces] + [rs.extent[5] for rs in self.sources])
+
+    def gap(self, z_start: float, z_end: float, eps: float) -> list:
+        """The free z range around z_start: from the last surface (or source end) before it to the first behind it (or z_end)."""
+        lo, hi = eps + max(rs.extent[5] for rs in self.sources), z_end - eps
+        for surf in self.surfaces:
+            if surf.z_max > z_start:
+                hi = surf.z_min
+                break
+            lo = surf.z_max
+        return [float(lo), float(hi)]
 
 
 def discrete_lines(sources) -> np.ndarray | None:

@@ -80,18 +80,31 @@ def surface_cases(ot) -> dict:
     return out
 
 
-def element_cases(ot) -> dict:
-    out = {}
+def elements(ot) -> tuple:
+    """-> (makers of the lenses, makers of the single-surface elements) of `element_cases`"""
     n = ot.RefractionIndex("Constant", n=1.5)
     mk = surfaces(ot)
+    lenses = {
+        "biconvex_de": lambda: ot.Lens(mk["sphere"](), ot.SphericalSurface(r=2.2, R=-7), de=0.3, pos=[0, 0, 10], n=n),
+        "meniscus_d": lambda: ot.Lens(mk["conic_pos"](), ot.ConicSurface(r=2, R=6, k=-0.5), d=1.1, pos=[1, 0, 5], n=n),
+        "d1_d2": lambda: ot.Lens(mk["circle"](), mk["conic"](), d1=0.4, d2=0.9, pos=[0, -1, 2], n=n),
+        "asphere_data": lambda: ot.Lens(mk["asphere"](), mk["data1d"](), de=0.25, pos=[0, 0, -4], n=n),
+        "tilted_pair": lambda: ot.Lens(mk["tilted"](), ot.TiltedSurface(r=2, normal=[-0.1, 0.25, 1]), de=0.5, pos=[0, 0, 0], n=n),
+    }
+    singles = {
+        "aperture": lambda: ot.Aperture(mk["ring"](), pos=[0, 1, 3]),
+        "filter": lambda: ot.Filter(mk["rect"](), pos=[1, 1, 4], spectrum=ot.TransmissionSpectrum("Constant", val=0.5)),
+        "detector": lambda: ot.Detector(mk["sphere"](), pos=[0, 0, 30]),
+        "ideal": lambda: ot.IdealLens(r=3, D=25, pos=[0, 0, 9]),
+        "source": lambda: ot.RaySource(mk["rect"](), pos=[0.5, 0, -5], s=[0.1, 0.2, 1]),
+    }
+    return lenses, singles
+
+
+def element_cases(ot) -> dict:
+    out = {}
+    lenses, singles = elements(ot)
     with ot.global_options.no_warnings():
-        lenses = {
-            "biconvex_de": lambda: ot.Lens(mk["sphere"](), ot.SphericalSurface(r=2.2, R=-7), de=0.3, pos=[0, 0, 10], n=n),
-            "meniscus_d": lambda: ot.Lens(mk["conic_pos"](), ot.ConicSurface(r=2, R=6, k=-0.5), d=1.1, pos=[1, 0, 5], n=n),
-            "d1_d2": lambda: ot.Lens(mk["circle"](), mk["conic"](), d1=0.4, d2=0.9, pos=[0, -1, 2], n=n),
-            "asphere_data": lambda: ot.Lens(mk["asphere"](), mk["data1d"](), de=0.25, pos=[0, 0, -4], n=n),
-            "tilted_pair": lambda: ot.Lens(mk["tilted"](), ot.TiltedSurface(r=2, normal=[-0.1, 0.25, 1]), de=0.5, pos=[0, 0, 0], n=n),
-        }
         for name, make in lenses.items():
             L = make()
             out[f"lens/{name}/new"] = element_state(L)
@@ -103,13 +116,6 @@ def element_cases(ot) -> dict:
             out[f"lens/{name}/flipped_back"] = surface_state(L.back)
             L.rotate(-40.0)
             out[f"lens/{name}/rotated"] = element_state(L)
-        singles = {
-            "aperture": lambda: ot.Aperture(mk["ring"](), pos=[0, 1, 3]),
-            "filter": lambda: ot.Filter(mk["rect"](), pos=[1, 1, 4], spectrum=ot.TransmissionSpectrum("Constant", val=0.5)),
-            "detector": lambda: ot.Detector(mk["sphere"](), pos=[0, 0, 30]),
-            "ideal": lambda: ot.IdealLens(r=3, D=25, pos=[0, 0, 9]),
-            "source": lambda: ot.RaySource(mk["rect"](), pos=[0.5, 0, -5], s=[0.1, 0.2, 1]),
-        }
         for name, make in singles.items():
             el = make()
             el.move_to([2, -1, 6.5])
