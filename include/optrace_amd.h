@@ -423,10 +423,21 @@ int ot_rays_fill_index(const ot_scene* scene, const ot_rays* rays, int64_t first
  * its rays on the device is a function of (scene, sources, ranges, seed) alone, so with the arguments of that trace the
  * planes are bit for bit what it stores without OT_DEFER_POL.  `ranges` must cover the storage as they did for the trace,
  * rays->nt must be the scene's section count and the scene must track polarisation; only rays->N, nt and pol are used.
- * Counters are not touched and a hit-search timeout is not reported.  Asynchronous on `stream`. */
+ * Counters are not touched and a hit-search timeout is not reported.  Asynchronous on `stream`.
+ * OT_DEFER_SECTIONS: ot_generate_and_trace and ot_generate_and_trace_host write rays->p and rays->w for the last two sections
+ * only (nt - 2 and nt - 1: what a detector behind the last surface and ot_tail_append read); s, wl and the counters as
+ * before.  ot_trace stores every section whatever the mask.  ot_rays_fill_sections writes p and w of the sections
+ * [0, nt - 2) of the rays [first, first + count) by repeating the trace with its arguments, bit for bit what the trace
+ * stores without the bit, frozen and NaN positions of absorbed rays included; it rewrites s and wl with the values they
+ * have.  rays->nt must be the scene's section count; rays->N, nt, p, w, s and wl are used, n and pol are not.  The scene's
+ * counters, its pinned counter buffer and its timing events (ot_scene_last_trace_ms) are left as the trace set them, and a
+ * hit-search timeout is not reported.  Asynchronous on `stream`.  A reader of the early sections pays one more trace. */
 #define OT_DEFER_INDEX 1u
 #define OT_DEFER_POL 2u
+#define OT_DEFER_SECTIONS 4u
 int ot_scene_set_deferred_planes(ot_scene* scene, uint32_t mask);
+int ot_rays_fill_sections(const ot_scene* scene, const ot_sources* sources, const ot_source_range* ranges, int32_t n_ranges,
+                          uint64_t seed, const ot_rays* rays, int64_t first, int64_t count, void* stream);
 int ot_rays_fill_pol(const ot_scene* scene, const ot_sources* sources, const ot_source_range* ranges, int32_t n_ranges,
                      uint64_t seed, const ot_rays* rays, int64_t first, int64_t count, void* stream);
 

@@ -111,7 +111,7 @@ struct ot_scene {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
     // ot_scene_set_deferred_planes: OT_DEFER_* bits of the planes the generating trace kernels leave unwritten (ot_rays.n:
-    // ot_rays_fill_index writes it; ot_rays.pol: ot_rays_fill_pol)
+    // ot_rays_fill_index writes it; ot_rays.pol: ot_rays_fill_pol; p and w before section nt - 2: ot_rays_fill_sections)
     uint32_t deferred = 0;
     // SPEC of the last stored trace (0 formulas, 1 + tables, 2 per-line tables; -1: none yet): ot_rays_fill_index evaluates
     // the indices the way that launch did

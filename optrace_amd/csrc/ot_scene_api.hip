@@ -490,10 +490,11 @@ extern "C" int ot_scene_set_timing(ot_scene* sc, int32_t on) {
 
 // The index plane ot_rays.n is a function of (scene, section, wavelength) alone and nothing in the library reads it: a caller
 // who does not need it after every trace switches its stores off and writes it with ot_rays_fill_index when it is asked for.
-// The polarisation planes can be repeated from (scene, sources, ranges, seed) by ot_rays_fill_pol.  One mask holds both.
+// The polarisation planes can be repeated from (scene, sources, ranges, seed) by ot_rays_fill_pol, and so can position and
+// weight of the sections before the last two (OT_DEFER_SECTIONS, ot_rays_fill_sections).  One mask holds all three.
 extern "C" int ot_scene_set_deferred_planes(ot_scene* sc, uint32_t mask) {
     if (!sc) return fail(OT_ERR_INVALID, "ot_scene_set_deferred_planes: null scene");
-    if (mask & ~(uint32_t)(OT_DEFER_INDEX | OT_DEFER_POL)) return fail(OT_ERR_INVALID, "ot_scene_set_deferred_planes: unknown bit in the mask");
+    if (mask & ~(uint32_t)(OT_DEFER_INDEX | OT_DEFER_POL | OT_DEFER_SECTIONS)) return fail(OT_ERR_INVALID, "ot_scene_set_deferred_planes: unknown bit in the mask");
     sc->deferred = mask;
     return OT_OK;
 }

@@ -344,8 +344,8 @@ OT_DEV void store_f32(const void* base, uint32_t off, float v) {
 // formed once per ray.  The offsets are 32 bits wide: a launch covers at most 2^28 rays (the host entry points
 // split longer bundles and advance the base pointers).
 template <bool POL>
-OT_DEV void store_section(const ot_rays& R, uint32_t o8, uint32_t o4, int sec, const V3& p, float w, double n, float px,
-                          float py, float pz) {
+OT_DEV void store_section(const ot_rays& R, uint32_t o8, uint32_t o4, int sec, bool pw, const V3& p, float w, double n,
+                          float px, float py, float pz) {
     // Measured on the bench scene, same box (profiles/r2/store_variants.txt): this form 1.676 ms, per-plane 64-bit
     // VGPR addresses 1.700 ms, a wave-tiled layout ([tile of 64 rays][section][component][lane] inside each array)
     // 1.682 ms -- so the reference's planar Fortran layout stays and host views need no re-ordering.  Without the
@@ -353,10 +353,12 @@ OT_DEV void store_section(const ot_rays& R, uint32_t o8, uint32_t o4, int sec, c
     // do overlap, but together they run into the package power limit.
     const int64_t N = R.N;
     const int64_t nt = R.nt;
-    store_f64(R.p + N * sec, o8, p.x);
-    store_f64(R.p + N * (sec + nt), o8, p.y);
-    store_f64(R.p + N * (sec + 2 * nt), o8, p.z);
-    store_f32(R.w + N * sec, o4, w);
+    if (pw) {  // (see store_section_next)
+        store_f64(R.p + N * sec, o8, p.x);
+        store_f64(R.p + N * (sec + nt), o8, p.y);
+        store_f64(R.p + N * (sec + 2 * nt), o8, p.z);
+        store_f32(R.w + N * sec, o4, w);
+    }
     if (R.n) store_f64(R.n + N * sec, o8, n);  // (null: see store_section_next)
     if (POL && R.pol) {
         store_f32(R.pol + N * sec, o4, px);
@@ -391,12 +393,18 @@ OT_DEV void store_pol_next(PlaneBases& b, uint32_t o4, float px, float py, float
     b.qx += b.N, b.qy += b.N, b.qz += b.N;
 }
 template <bool POL>
-OT_DEV void store_section_next(PlaneBases& b, uint32_t o8, uint32_t o4, const V3& p, float w, double n, float px, float py,
-                               float pz) {
-    store_f64(b.px, o8, p.x);
-    store_f64(b.py, o8, p.y);
-    store_f64(b.pz, o8, p.z);
-    store_f32(b.w, o4, w);
+OT_DEV void store_section_next(PlaneBases& b, uint32_t o8, uint32_t o4, bool pw, const V3& p, float w, double n, float px,
+                               float py, float pz) {
+    // Position and weight (28 B per section): nothing between a generating trace and an image reads them before section
+    // nt - 2, and such a trace can be repeated.  With OT_DEFER_SECTIONS the launcher hands in the range of sections whose
+    // planes this launch writes -- [nt - 2, nt) for the trace, [0, nt - 2) for ot_rays_fill_sections -- and `pw` says
+    // whether this section lies in it: section and range are wave-uniform, a scalar branch.  The bases advance either way.
+    if (pw) {
+        store_f64(b.px, o8, p.x);
+        store_f64(b.py, o8, p.y);
+        store_f64(b.pz, o8, p.z);
+        store_f32(b.w, o4, w);
+    }
     // The index plane is a function of (scene, section, wavelength) alone: with the scene's index store switched off
     // (ot_scene_set_index_store) the launcher hands in a null base, the plane stays unwritten -- 8 of 52 B per section
     // with polarisation -- and ot_rays_fill_index writes it when somebody reads it.  The base is a kernel argument: a
@@ -436,13 +444,15 @@ struct TailState {
 };
 // What trace_ray stores: every plane (trace_kernel) / nothing, the TAIL form above / the polarisation planes alone
 // (trace_pol_kernel: the replay behind ot_rays_fill_pol -- the same arithmetic, `R` needs pol, N and nt only).
+// [sec_first, sec_end): with OT_STORE_ALL, the sections whose position and weight planes are written (store_section_next).
 #define OT_STORE_ALL 0
 #define OT_STORE_NONE 1
 #define OT_STORE_POL 2
 template <bool POL, int SPEC, int FEAT, int STORE = OT_STORE_ALL, class SC>
 OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, RayState& r,
                       const double* __restrict__ hurb_normals, uint64_t seed, unsigned int* msgs, const double* ltab,
-                      int lj, double* patch_lds, TailState* tail = nullptr) {
+                      int lj, double* patch_lds, TailState* tail = nullptr, int sec_first = 0,
+                      int sec_end = 0x7fffffff) {
     constexpr bool TAB = (SPEC == 1);
     constexpr bool TAIL = (STORE == OT_STORE_NONE);
     constexpr bool ALL = (STORE == OT_STORE_ALL);
@@ -475,10 +485,12 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
 #if OT_RUNNING_BASES
     PlaneBases planes = {};
     if (!TAIL) planes = plane_bases<POL>(R);
-    if (ALL) store_section_next<POL>(planes, o8, o4, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+    if (ALL)
+        store_section_next<POL>(planes, o8, o4, sec_first <= 0 && 0 < sec_end, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
     if (POL_ONLY) store_pol_next(planes, o4, r.polx, r.poly, r.polz);
 #else
-    if (ALL) store_section<POL>(R, o8, o4, 0, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+    if (ALL)
+        store_section<POL>(R, o8, o4, 0, sec_first <= 0 && 0 < sec_end, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
 #endif
 
     for (int i = 0; i < sc.n_steps; i++) {  // i = index of the section the ray starts this step in
@@ -568,10 +580,14 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
 #endif
         {
 #if OT_RUNNING_BASES
-            if (ALL) store_section_next<POL>(planes, o8, o4, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+            if (ALL)
+                store_section_next<POL>(planes, o8, o4, sec_first <= i + 1 && i + 1 < sec_end, r.p, r.w, r.n_cur, r.polx,
+                                        r.poly, r.polz);
             if (POL_ONLY) store_pol_next(planes, o4, r.polx, r.poly, r.polz);
 #else
-            if (ALL) store_section<POL>(R, o8, o4, i + 1, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+            if (ALL)
+                store_section<POL>(R, o8, o4, i + 1, sec_first <= i + 1 && i + 1 < sec_end, r.p, r.w, r.n_cur, r.polx,
+                                   r.poly, r.polz);
 #endif
         }
     }

@@ -1,6 +1,6 @@
 // C-ABI, trace stage: ray generation, the launches of the trace kernel's three forms (ot_trace_kernel.hpp, instantiated in
-// ot_trace_f*.hip / ot_trace_t*.hip / ot_trace_p*.hip), the counter reduction, the index and polarisation fills and the
-// render-only tail storage.
+// ot_trace_f*.hip / ot_trace_t*.hip / ot_trace_p*.hip), the counter reduction, the index, polarisation and section fills and
+// the render-only tail storage.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -148,6 +148,8 @@ static TraceLaunch make_launch(const ot_scene* sc, const ot_sources* src, const 
     L.pol = !sc->h.no_pol;
     L.gen = src != nullptr;
     L.spec = v.spec;
+    L.sec_first = 0;
+    L.sec_end = sc->h.nt;
     return L;
 }
 
@@ -220,6 +222,9 @@ static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const Range
     sc->index_spec = v.spec;  // what ot_rays_fill_index has to repeat
     TraceLaunch L = make_launch(sc, src, rg, v, seed, (hipStream_t)stream);
     L.hurb_normals = hurb_normals;
+    // OT_DEFER_SECTIONS: position and weight of the last two sections only, which is all a detector behind the stack and
+    // ot_tail_append read; ot_rays_fill_sections writes the rest.  Rays handed in cannot be repeated: every section.
+    if ((sc->deferred & OT_DEFER_SECTIONS) && src) L.sec_first = std::max(0, sc->h.nt - 2);
     return trace_chunks(sc, rays->N, msgs, L.st, [&](int64_t base, uint32_t n) {
         L.part = *rays;
         L.part.p += base; L.part.s += base; L.part.w += base; L.part.n += base; L.part.wl += base;
@@ -338,6 +343,38 @@ extern "C" int ot_rays_fill_pol(const ot_scene* sc, const ot_sources* src, const
     for_ray_chunks(first, count, [&](int64_t base, uint32_t n) {
         L.part.pol = rays->pol + base;
         launch_chunk(OT_FORM_POL, v.feat, L, base, n);
+    });
+    HIP_TRY(hipGetLastError());
+    return OT_OK;
+}
+
+// The position and weight planes of the sections a trace left unwritten (OT_DEFER_SECTIONS): the storing kernel of that trace
+// once more (trace_variant), writing p and w of the sections [0, nt - 2) -- and, with the same values as before, s and wl.
+// The index and polarisation planes are not touched, the counters stay in the workgroups (null slot table), the scene's
+// pinned counters and its timing events are left as the trace set them.
+extern "C" int ot_rays_fill_sections(const ot_scene* sc, const ot_sources* src, const ot_source_range* ranges, int32_t n_ranges,
+                                     uint64_t seed, const ot_rays* rays, int64_t first, int64_t count, void* stream) {
+    if (!sc || !src || !ranges || !rays) return fail(OT_ERR_INVALID, "ot_rays_fill_sections: null argument");
+    if (rays->N < 0 || !rays->p || !rays->w || !rays->s || !rays->wl)
+        return fail(OT_ERR_INVALID, "ot_rays_fill_sections: the ray storage needs p, w, s and wl");
+    if (int rc = check_sections("ot_rays_fill_sections", sc, rays)) return rc;
+    if (first < 0 || count < 0 || first > rays->N || count > rays->N - first)
+        return fail(OT_ERR_INVALID, "ot_rays_fill_sections: range outside the storage");
+    if (int rc = require_device()) return rc;
+    const RangeArgs* rg = nullptr;
+    if (int rc = make_ranges(ranges, n_ranges, src, rays->N, &rg)) return rc;
+    if (rays->nt < 3 || count == 0) return OT_OK;  // nothing is ever left out of two sections
+    const TraceVariant v = trace_variant(sc, src, nullptr);
+    if (v.error) return fail(OT_ERR_UNSUPPORTED, v.error);
+    TraceLaunch L = make_launch(sc, src, rg, v, seed, (hipStream_t)stream);
+    L.slots = nullptr;
+    L.sec_end = rays->nt - 2;
+    for_ray_chunks(first, count, [&](int64_t base, uint32_t n) {
+        L.part = *rays;
+        L.part.p += base; L.part.s += base; L.part.w += base; L.part.wl += base;
+        L.part.n = nullptr;
+        L.part.pol = nullptr;
+        launch_chunk(OT_FORM_STORE, v.feat, L, base, n);
     });
     HIP_TRY(hipGetLastError());
     return OT_OK;

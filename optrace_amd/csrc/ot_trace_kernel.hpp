@@ -215,9 +215,11 @@ OT_DEV double* patch_base(double* lds, TraceLds f) {
     return (FEAT / 2 >= OT_HIT_SPLINE) ? lds + f.n_tab + (f.n_cnt + 2) / 2 : nullptr;
 }
 
-// the workgroup's counters go to its slot table (blockIdx % slots), once every wave is through
+// the workgroup's counters go to its slot table (blockIdx % slots), once every wave is through.  slots null: they go
+// nowhere (ot_rays_fill_sections: the trace that is being repeated has reported them, its timeout flag included)
 OT_DEV void flush_counters(TraceLds f, unsigned int* slots) {
     __syncthreads();
+    if (!slots) return;
     unsigned int* slot = slots + (size_t)(blockIdx.x % OT_CNT_SLOTS) * f.n_cnt;
     for (int k = threadIdx.x; k < f.n_cnt; k += blockDim.x)
         if (f.cnt[k]) atomicAdd(&slot[k], f.cnt[k]);
@@ -236,12 +238,14 @@ OT_DEV void flush_counters(TraceLds f, unsigned int* slots) {
 // reduce_counters_kernel, so that no two workgroups hammer the same address (see count_event).
 // The launch covers the rays [ray_base, ray_base + count) of the bundle; R's pointers are advanced to ray_base by
 // the host (R.N stays the plane stride), so lanes address their ray with a 32-bit offset (count <= 2^28).
+// [sec_first, sec_end): the sections whose position and weight planes this launch writes (ot_trace.hpp::store_section_next) --
+// all of them, the last two (OT_DEFER_SECTIONS) or all but those (ot_rays_fill_sections); kernel arguments, so wave-uniform.
 template <bool POL, bool GEN, int SPEC, int FEAT>
 __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_kernel(const SceneDev* __restrict__ scp, ot_rays R,
                                                     const SourceDev* __restrict__ sources, RangeArgs rg,
                                                     const double* __restrict__ hurb_normals, uint64_t seed,
                                                     unsigned int* __restrict__ slots, int64_t ray_base,
-                                                    uint32_t count) {
+                                                    uint32_t count, int sec_first, int sec_end) {
     extern __shared__ double lds[];  // (TraceLds)
     auto& sc = *as_const(scp);
     const TraceLds f = trace_lds_init<SPEC>(lds, sc);
@@ -282,7 +286,7 @@ __global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_ke
     if (have) {
         const int lj = ray_line<SPEC>(sc, f.ltab, r.wl);
         bool ok = trace_ray<POL, SPEC, FEAT>(sc, R, local, (uint64_t)ray, r, hurb_normals, seed, f.cnt, f.ltab, lj,
-                                             patch_base<FEAT>(lds, f));
+                                             patch_base<FEAT>(lds, f), nullptr, sec_first, sec_end);
         if (!ok) f.cnt[f.n_cnt - 1] = 1u;  // numeric hit search timed out (surface.py:403)
     }
     flush_counters(f, slots);
@@ -432,6 +436,7 @@ struct TraceLaunch {
     uint32_t count;
     bool pol, gen;
     int spec;
+    int sec_first, sec_end;  // OT_FORM_STORE: sections whose position and weight planes are written (make_launch: all)
 };
 
 // The launcher of one form and feature level: L.spec, L.pol and (storing form) L.gen pick the kernel.  Defined in
@@ -451,10 +456,10 @@ static void launch_trace_kernel(const TraceLaunch& L) {
                            L.count);
     else if (L.gen)
         hipLaunchKernelGGL((trace_kernel<POL, true, SPEC, FEAT>), L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg,
-                           L.hurb_normals, L.seed, L.slots, L.base, L.count);
+                           L.hurb_normals, L.seed, L.slots, L.base, L.count, L.sec_first, L.sec_end);
     else if constexpr (SPEC != 2)  // (discrete spectra: generated rays only, see trace_variant)
         hipLaunchKernelGGL((trace_kernel<POL, false, SPEC, FEAT>), L.grid, block, L.lds, L.st, L.sc, L.part, L.sd, *L.rg,
-                           L.hurb_normals, L.seed, L.slots, L.base, L.count);
+                           L.hurb_normals, L.seed, L.slots, L.base, L.count, L.sec_first, L.sec_end);
 }
 
 template <int FORM, int FEAT, int SPEC>

@@ -61,6 +61,24 @@ HitList = namedtuple("HitList", "ph hw extent ill_count wl fill")
 DetectorHits = namedtuple("DetectorHits", "xy w wl extent projection ill_count label fill")
 
 
+def rays_for(rays, surfs) -> _capi.Rays:
+    """The `ot_rays` of `rays` for a launch of the detector stage against the detector surfaces `surfs` (`_capi.Surface` at
+    the positions asked for): THE rule for when the sections a trace left out (OT_DEFER_SECTIONS, everything before
+    section nt - 2) need not be written first.  The section search of `ot_detector.hpp::detector_hit` reads a plane before
+    nt - 2 only for a ray with z[nt - 2] >= z_min of its detector; every other ray is settled from the last two sections
+    (`detector_hit_last`, the first branch of the search).  So no ray reads an early plane if all of this holds:
+      - every detector's z_min lies behind the largest z_max of the tracing surfaces: at section nt - 2 a ray stands on
+        the last surface, or rests where it was absorbed on an earlier one (a NaN position compares false as well);
+      - the OUTLINE_INTERSECTION counters of the trace are all zero: a clipped ray rests somewhere on the outline box;
+      - the storage has nt >= 3 (with fewer nothing is left out).
+    The trace states the last two as `RayStorage._tail_z`.  Otherwise, and always once the sections are filled, the storage
+    is complete when this returns.  A `TailStorage` has two sections and nothing to fill."""
+    if not hasattr(rays, "_sections_stale"):
+        return rays._rays_struct()
+    z = rays._tail_z
+    return rays._rays_struct(tail_only=z is not None and rays._nt >= 3 and all(float(s.z_min) > z for s in surfs))
+
+
 def batches(requests: list):
     """The launches of a list of requests: grouped by ray range in order of first appearance, at most `_capi.DET_MAX` per
     launch.  -> (indices into `requests`, those requests) per launch."""
@@ -138,7 +156,7 @@ def detector_hits_multi(rays, first: int, count: int, requests: list, extent_onl
         r.extent4 = mb_t.data_ptr() + 8 * ext if ext is not None else None
         r.wl_out, r.fill = (wl_c.data_ptr(), fill.data_ptr()) if compact else (None, None)
         outs.append((ph, hw, ext, wl_c, fill))
-    rs = rays._rays_struct()
+    rs = rays_for(rays, [rq.surf for rq in requests])
     _capi.check(lib.ot_detector_hits_multi(C.byref(rs), int(first), int(count), reqs, n, stream_ptr()))
     ill_h = _ill_counts(ill, requests)
     if any(o[2] is not None for o in outs):
@@ -163,7 +181,7 @@ def detector_extent_sample(rays, first: int, count: int, surf_desc: _capi.Surfac
     lib = _capi.load_library()
     require_device()
     mb_t, mb = mailbox()
-    rs = rays._rays_struct()
+    rs = rays_for(rays, [surf_desc])
     _capi.check(lib.ot_detector_extent_sample(C.byref(rs), int(first), int(count), C.byref(surf_desc), int(projection),
                                               int(stride), C.c_void_p(mb_t.data_ptr()), stream_ptr()))
     return mb.view(np.float64)[:4].copy()  # (the call waits for the stream)
@@ -181,7 +199,7 @@ class AutoImage:
         self._lib = _capi.load_library()
         require_device()
         mb_t, mb = mailbox()
-        rs = rays._rays_struct()
+        rs = rays_for(rays, [surf_desc])
         origin = (C.c_double * 2)(float(grid[0]), float(grid[1]))
         tile = (C.c_double * 2)(float(grid[2]), float(grid[3]))
         tiles = (C.c_int32 * 2)(int(grid[4]), int(grid[5]))
@@ -229,7 +247,7 @@ def detector_images(rays, first: int, count: int, requests: list) -> list:
         r.extent[:] = [float(v) for v in rq.extent]
         r.hist = rq.hist.data_ptr()
         r.weight_scale = float(rq.weight_scale)
-    rs = rays._rays_struct()
+    rs = rays_for(rays, [rq.surf for rq in requests])
     _capi.check(lib.ot_detector_images(C.byref(rs), int(first), int(count), reqs, n, stream_ptr()))
     return [int(v) for v in _ill_counts(ill, requests)[0::2]]  # (no read-back, no sync for closed-form detectors)
 

@@ -222,7 +222,7 @@ def sharded_detector_image(RT, N: int, detector_index: int = 0, extent=None, pro
         RT.trace(n_local, _power_scale=n_local / N)
     finally:
         RT.seed = seed0
-    dev = RT.rays._dev["p"].device
+    dev = RT.rays._dev["s"].device  # (an entry without a fill hook: the device is all that is asked)
     spec = dict(detector_index=detector_index, source_index=None, extent=extent, projection_method=projection_method)
     if extent is None:
         # agree on the automatic extent first: extent-only pass over the sections, min / max exchange, then the binning

@@ -121,9 +121,10 @@ class TailStorage:
         ot_tail_capacity(tail rays + chunk rays + 64) before the tail was traced)."""
         lib = _capi.load_library()
         mb_t, mb = mailbox()
-        _capi.check(lib.ot_tail_append(C.byref(rays._rays_struct()), 0, int(rays.N), float(weight_scale), int(self.traced),
-                                       C.byref(self._rays_struct()), ptr(self._dev["fill"]), C.c_void_p(mb_t.data_ptr()),
-                                       stream_ptr()))
+        # (`ot_tail_append` reads the last two sections only: no fill of the sections a trace left out)
+        _capi.check(lib.ot_tail_append(C.byref(rays._rays_struct(tail_only=True)), 0, int(rays.N), float(weight_scale),
+                                       int(self.traced), C.byref(self._rays_struct()), ptr(self._dev["fill"]),
+                                       C.c_void_p(mb_t.data_ptr()), stream_ptr()))
         self.N, self.alive, self.traced = int(mb[0]), int(mb[1]), self.traced + int(rays.N)
 
     def release(self) -> None:
@@ -146,9 +147,10 @@ class SceneRef:
 
 
 class _DeviceBuffers(dict):
-    """name -> flat device tensor of a `RayStorage`.  A plain dict but for the keys "n" and "pol": the tracer's scenes leave
-    the index plane and the polarisation planes unwritten (`ot_scene_set_deferred_planes`), so reading one of these entries
-    first lets the storage fill it (`_ensure_index`, `_ensure_pol`)."""
+    """name -> flat device tensor of a `RayStorage`.  A plain dict but for the keys "n", "pol", "p" and "w": the tracer's
+    scenes leave the index plane, the polarisation planes and position and weight of all but the last two sections unwritten
+    (`ot_scene_set_deferred_planes`), so reading one of these entries first lets the storage fill it (`_ensure_index`,
+    `_ensure_pol`, `_ensure_sections`).  `dict.__getitem__(d, key)` goes past the hook: the tensor, whatever it holds."""
 
     __slots__ = ("_owner",)
 
@@ -165,6 +167,10 @@ class _DeviceBuffers(dict):
             owner = self._owner()
             if owner is not None:
                 owner._ensure_pol()
+        elif key == "p" or key == "w":
+            owner = self._owner()
+            if owner is not None:
+                owner._ensure_sections()
 
     def __getitem__(self, key):
         self._touch(key)
@@ -209,6 +215,11 @@ class RayStorage(BaseClass):
         # keeps scene, table and ranges alive until the planes are filled or another trace overwrites the mark
         # (`_pol_pending`, `_ensure_pol`).
         self._pol_stale = None
+        # Position and weight of the sections before the last two, `_dev["p"]` and `_dev["w"]`, likewise and with a mark of
+        # the same kind (`_sections_pending`, `_ensure_sections`); the two fills are independent.  `_tail_z`: detectors
+        # whose z_min lies behind it see this storage through its last two sections alone (`_tail_proof`); None: not shown.
+        self._sections_stale = None
+        self._tail_z = None
         self._powers = []
         self._ranges = None   # ot_source_range array of the current split (`_source_ranges`)
         self._rays_c = None   # ot_rays of the current buffers
@@ -254,12 +265,14 @@ class RayStorage(BaseClass):
             d["_dev"], d["_rays_c"], d["_host"] = _DeviceBuffers(self), None, {}
             d["_N"], d["_Np"], d["_nt"] = N, N, nt
             d["_n_stale"], d["_n_scene"], d["_pol_stale"] = False, None, None
+            d["_sections_stale"], d["_tail_z"] = None, None
             return
         Np = -(-N // self.PAD_TO) * self.PAD_TO if N >= self.PAD_FROM else N
         old = self._dev
-        # (whether there are polarisation planes, not what they hold: read past the hook of `_dev`, no fill)
+        # (whether there are polarisation planes and where the buffers live, not what they hold: read past the hook of `_dev`,
+        # no fill -- through the hook every trace into kept buffers would first repeat the one before it)
         reuse = bool(old and self._N == N and self._Np == Np and self._nt == nt
-                     and (dict.get(old, "pol") is None) == bool(no_pol) and old["p"].device == dev)
+                     and (dict.get(old, "pol") is None) == bool(no_pol) and dict.__getitem__(old, "p").device == dev)
         del old
         if not reuse:
             # (a trace with the shape of the previous one writes into the same buffers: host views already handed
@@ -267,6 +280,7 @@ class RayStorage(BaseClass):
             d["_dev"] = _DeviceBuffers(self)  # the previous storage goes back to the allocator before the new one is requested
             d["_n_stale"], d["_n_scene"] = True, None  # a fresh plane: nothing to fill it from until a trace says so
             d["_pol_stale"] = None
+            d["_sections_stale"], d["_tail_z"] = None, None
 
             def alloc() -> dict:
                 return {
@@ -314,16 +328,22 @@ class RayStorage(BaseClass):
         return self._nt if self.N_list.shape[0] else 0
 
     # ---- device side --------------------------------------------------------------------------------
-    def _rays_struct(self) -> _capi.Rays:
+    def _rays_struct(self, tail_only: bool = False) -> _capi.Rays:
+        """The `ot_rays` of the buffers, for a native entry point that may read any section of p and w: the sections a trace
+        left out are filled first (`_ensure_sections`).  `tail_only`: for a caller that writes the buffers or reads nothing
+        before section nt - 2 -- the trace launch, `TailStorage.append_living`, the detector stage under
+        `detector.rays_for` -- no fill.  The index plane and the polarisation planes are never filled here."""
+        if not tail_only and self._sections_stale is not None:
+            self._ensure_sections()
         if self._rays_c is not None:
             return self._rays_c
         d = self._dev
         r = _capi.Rays()
         r.N, r.nt = self._Np, self._nt  # the plane stride; how many rays there are, the ranges / counts of each call say
-        # (the addresses of the index plane and the polarisation planes, not their contents: read past the hook of `_dev`,
-        # no fill)
-        r.p, r.s, r.w, r.n, r.wl = (d["p"].data_ptr(), d["s"].data_ptr(), d["w"].data_ptr(),
-                                    dict.__getitem__(d, "n").data_ptr(), d["wl"].data_ptr())
+        # (addresses, not contents: read past the hook of `_dev`, no fill)
+        raw = dict.__getitem__
+        r.p, r.s, r.w, r.n, r.wl = (raw(d, "p").data_ptr(), d["s"].data_ptr(), raw(d, "w").data_ptr(),
+                                    raw(d, "n").data_ptr(), d["wl"].data_ptr())
         pol = dict.__getitem__(d, "pol")
         r.pol = pol.data_ptr() if pol is not None else None
         self.__dict__["_rays_c"] = r
@@ -341,8 +361,8 @@ class RayStorage(BaseClass):
         scene = self._n_scene
         if not self._n_stale or scene is None:
             return
-        _capi.check(_capi.load_library().ot_rays_fill_index(scene.handle, C.byref(self._rays_struct()), 0, self._n_count,
-                                                            stream_ptr()))
+        _capi.check(_capi.load_library().ot_rays_fill_index(scene.handle, C.byref(self._rays_struct(tail_only=True)), 0,
+                                                            self._n_count, stream_ptr()))
         d = self.__dict__  # (after the launch: a call that fails leaves the plane marked and its scene held)
         d["_n_stale"], d["_n_scene"] = False, None
 
@@ -362,8 +382,39 @@ class RayStorage(BaseClass):
             return
         scene, table, ranges, seed, count = mark
         _capi.check(_capi.load_library().ot_rays_fill_pol(scene.handle, table.handle, ranges, len(ranges), seed,
-                                                          C.byref(self._rays_struct()), 0, count, stream_ptr()))
+                                                          C.byref(self._rays_struct(tail_only=True)), 0, count, stream_ptr()))
         self.__dict__["_pol_stale"] = None  # (after the launch: a call that fails leaves the planes marked)
+
+    def _sections_pending(self, scene: SceneRef, table: "SourceTable", ranges, seed: int, count: int) -> None:
+        """A trace of `scene` that generates its rays from (`table`, `ranges`, `seed`) is about to write this storage and
+        stores position and weight of the last two sections only (OT_DEFER_SECTIONS): the sections before them of rays
+        [0, count) are to be written by repeating that trace when `p` or `w` is read.  `scene=None` clears the mark (rays
+        handed in: `ot_trace` stores every section).  A second trace into the same buffers replaces the mark without a
+        fill: what the first one left out is overwritten or left out again.  The storage holds scene, table and ranges until
+        the fill or the next mark.  Whatever was known about the previous rays (`_tail_z`) goes with them."""
+        keep = scene is not None and self._nt >= 3  # (two sections: nothing is left out)
+        d = self.__dict__
+        d["_sections_stale"] = (scene, table, ranges, int(seed), int(count)) if keep else None
+        d["_tail_z"] = None
+
+    def _tail_proof(self, z_last: float, clipped: bool) -> None:
+        """What the trace that just wrote this storage knows about section nt - 2: the rays start it on a tracing surface
+        or rest on an earlier one, none of which reaches behind `z_last` -- unless a ray was `clipped` at the outline
+        (OUTLINE_INTERSECTION counted), which rests somewhere on the outline box."""
+        self.__dict__["_tail_z"] = None if clipped or self._nt < 3 else float(z_last)
+
+    def _ensure_sections(self) -> None:
+        """Write position and weight of the sections a trace left out, if any (`ot_rays_fill_sections`: the trace once
+        more on the current stream; no synchronisation, no host copy, counters and timing of the trace untouched).  Called
+        by `_dev` whenever its entry "p" or "w" is read, and by `_rays_struct`.  Independent of `_ensure_pol`."""
+        mark = self._sections_stale
+        if mark is None:
+            return
+        scene, table, ranges, seed, count = mark
+        _capi.check(_capi.load_library().ot_rays_fill_sections(scene.handle, table.handle, ranges, len(ranges), seed,
+                                                               C.byref(self._rays_struct(tail_only=True)), 0, count,
+                                                               stream_ptr()))
+        self.__dict__["_sections_stale"] = None  # (after the launch: a call that fails leaves the sections marked)
 
     _MIN_BLOCK = MIN_BLOCK
 
@@ -432,7 +483,8 @@ class RayStorage(BaseClass):
         seed = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         tab = self._source_table(seed)
         rng = self._source_ranges()
-        rays = self._rays_struct()
+        self.__dict__["_sections_stale"] = None  # (section 0 is written here: nothing of an earlier trace is worth a fill)
+        rays = self._rays_struct(tail_only=True)
         _capi.check(lib.ot_rays_generate(tab.handle, rng, len(rng), seed, int(self.no_pol), C.byref(rays),
                                          stream_ptr()))
         torch.cuda.current_stream().synchronize()
@@ -442,6 +494,8 @@ class RayStorage(BaseClass):
         """Inject section 0 from host arrays (used for parity runs against recorded reference rays)."""
         N, Np, nt, dev = self._N, self._Np, self._nt, require_device()
         self.__dict__["_pol_stale"] = None  # section 0 of the planes is written here, the rest by the trace of these rays
+        # (before the planes are touched: `d["p"]` below goes through the hook and must not repeat a trace it overwrites)
+        self.__dict__["_sections_stale"], self.__dict__["_tail_z"] = None, None
         d = self._dev
         p = np.asarray(p, dtype=np.float64)
         if Np > N:  # ot_trace walks the whole stride: the padding carries dead rays (weight 0, a valid direction)

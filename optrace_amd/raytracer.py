@@ -50,13 +50,14 @@ from . import checks as _checks
 class _TraceRecord:
     """What a full trace established, valid while `Raytracer._scene_unchanged()`.  The slow path of `trace` drops it as a
     whole: no split, range record or book-keeping of render-only traces outlives a change of the scene."""
-    __slots__ = ("epoch", "structure", "snap", "scene", "watch", "splits", "ranges", "book")
+    __slots__ = ("epoch", "structure", "snap", "scene", "watch", "splits", "ranges", "book", "z_last")
 
     def __init__(self, snap: dict, scene: CompiledScene, watch: list) -> None:
         self.epoch = self.structure = None  # mutation_epoch(), Raytracer._structure(): read when its trace is done
         self.snap, self.scene, self.watch = snap, scene, watch  # tracing_snapshot(), [(small writeable array, its bytes)]
         self.splits, self.ranges = {}, {}  # N -> split_rays(); (N, power scale) -> range records of a split without remainder
         self.book = None  # RayStorage without buffers: split, ranges and powers of render-only traces
+        self.z_last = None  # SectionTable.z_last() of this scene (`RayStorage._tail_proof`)
 
 
 class Raytracer(Group):
@@ -277,8 +278,11 @@ class Raytracer(Group):
         self._scene_handle = handle
         # Nothing reads the index plane or the polarisation planes on the way from a trace to an image, a spectrum or a
         # focus: the kernels leave them unwritten (20 of 48 B per section) and the storage fills them when `n_list` /
-        # `pol_list` is asked for (RayStorage._ensure_index, _ensure_pol)
-        _capi.check(lib.ot_scene_set_deferred_planes(handle, _capi.OT_DEFER_INDEX | _capi.OT_DEFER_POL))
+        # `pol_list` is asked for (RayStorage._ensure_index, _ensure_pol).  Position and weight before the last two sections
+        # are read by inspection and analysis, not by a detector behind the stack: left out as well (28 B per section) and
+        # written by a repeat of the trace when they are read (RayStorage._ensure_sections, detector.rays_for)
+        _capi.check(lib.ot_scene_set_deferred_planes(handle, _capi.OT_DEFER_INDEX | _capi.OT_DEFER_POL
+                                                     | _capi.OT_DEFER_SECTIONS))
         self._scene_key = key
         return self._scene
 
@@ -360,6 +364,7 @@ class Raytracer(Group):
             # before every shortcut (assignments move the counter, an edit in place like `RS.s[0] = 0.1` does not)
             publish = all(a.size < _base.SMALL_ARRAY for a in writeable)
             rec = _TraceRecord(snap, self._compile(key), [(a, a.tobytes()) for a in writeable] if publish else [])
+            rec.z_last = SectionTable(self).z_last()
         lib = _capi.load_library()
         dev = require_device()
 
@@ -384,7 +389,8 @@ class Raytracer(Group):
             rays_obj = rec.book
         rays_obj.init(self.ray_sources, N, nt, self.no_pol, _N_list=_N_list, _rng=rng, _power_scale=_power_scale,
                       _split=split, _ranges=rec.ranges.get(ranges_key), _alloc=_tail is None)
-        rays = rays_obj._rays_struct() if _tail is None else None
+        # (the trace writes the buffers: no fill of what the trace before it left out)
+        rays = rays_obj._rays_struct(tail_only=True) if _tail is None else None
         # a seeded tracer repeats itself call for call; the chunks of one iterative render must differ
         seed = int(np.random.randint(0, 2 ** 31 - 1)) if self.seed is None else int(self.seed) + 1000003 * int(_chunk)
 
@@ -416,6 +422,7 @@ class Raytracer(Group):
             else:
                 rays_obj._index_pending(self._scene_ref, N)
                 rays_obj._pol_pending(self._scene_ref, tab, rng_c, seed, N)
+                rays_obj._sections_pending(self._scene_ref, tab, rng_c, seed, N)
                 _capi.check(lib.ot_generate_and_trace_host(self._scene_handle, tab.handle, rng_c, len(rng_c), seed,
                                                            C.byref(rays), msgs_h.ctypes.data, stream_ptr()))
         else:
@@ -429,6 +436,7 @@ class Raytracer(Group):
             msgs = torch.zeros(n_msgs, dtype=torch.int64, device=dev)
             rays_obj._index_pending(self._scene_ref, rays_obj._Np)  # (ot_trace walks the whole stride)
             rays_obj._pol_pending(None, None, None, 0, 0)  # (and stores the polarisation planes itself)
+            rays_obj._sections_pending(None, None, None, 0, 0)  # (and every section)
             _capi.check(lib.ot_trace(self._scene_handle, C.byref(rays), ptr(hn), seed, ptr(msgs), stream_ptr()))
             msgs_h = msgs.cpu().numpy()  # (synchronises the stream)
 
@@ -445,6 +453,8 @@ class Raytracer(Group):
             self._msgs[self.INFOS.HURB_NEG_DIR, 0] = 0
             raise RuntimeError("All ray divergences s need to be in positive z-divergence")
         self._show_messages(N)
+        if _tail is None and _initial_rays is None:
+            rays_obj._tail_proof(rec.z_last + self.N_EPS, bool(self._msgs[self.INFOS.OUTLINE_INTERSECTION].any()))
         if _tail is None:  # (a render-only trace leaves `self.rays` and what is known about them alone)
             self._last_trace_snapshot = {**rec.snap, "Rays": [rays_obj.N, rays_obj.Nt, rays_obj.no_pol]}
         if publish and _initial_rays is None and not rays_obj._has_function_orientation:
