@@ -441,6 +441,23 @@ int ot_rays_fill_sections(const ot_scene* scene, const ot_sources* sources, cons
 int ot_rays_fill_pol(const ot_scene* scene, const ot_sources* sources, const ot_source_range* ranges, int32_t n_ranges,
                      uint64_t seed, const ot_rays* rays, int64_t first, int64_t count, void* stream);
 
+/* The step loop of the tracing kernels reads one compact "hot" record per step, compiled by ot_scene_create: the step,
+ * the surface constants of the closed-form hit and normal, and a form code that holds the host's evaluation of the
+ * wave-uniform decisions of that path (flat disc, ring, plain sphere, stable-root sphere, conic; OTHER = everything else,
+ * which reads the surface record as before).  ot_scene_set_hot_steps(scene, 0) rewrites the scene's table with every form
+ * OTHER, so that the same kernels take the surface-record path for every step; 1, the default, restores the forms.  The
+ * results are bit for bit the same either way: the switch exists to compare the two paths.  Works on the scene's device
+ * whichever device is current, and synchronises it.
+ * ot_scene_records_host needs no device: it compiles a scene description as ot_scene_create does and copies one table
+ * of records into `buf` -- table 0: the hot records (one per step and one of padding; hot_steps as above), 1: the surface
+ * records, 2: the step records, in the layouts of csrc/ot_scene.hpp.  `count` and `record_bytes` receive the number of
+ * records and the size of one; with buf == NULL nothing else happens. */
+int ot_scene_set_hot_steps(ot_scene* scene, int32_t on);
+/* the scene's hot records as its device holds them now: count = steps + 1 records of 192 bytes into buf */
+int ot_scene_read_hot_steps(const ot_scene* scene, void* buf, int64_t buf_bytes, int32_t* count);
+int ot_scene_records_host(const ot_scene_desc* desc, int32_t table, int32_t hot_steps, void* buf, int64_t buf_bytes,
+                          int32_t* count, int32_t* record_bytes);
+
 /* ---- leaf operators (public Surface / RefractionIndex methods) ---------------------------------- */
 /* Surface.find_hit (surface.py:307, conic_surface.py:126): p, s are (n,3) F-order device arrays;
  * outputs p_hit (n,3) F-order, is_hit (n) uint8, ill (n) uint8: bit 0 = ill-conditioned bracket

@@ -158,6 +158,9 @@ SIGNATURES = {
     "ot_scene_set_deferred_planes": (C.c_int, [vp, C.c_uint32]),
     "ot_rays_fill_pol": (C.c_int, [vp, vp, C.POINTER(SourceRange), i32, u64, C.POINTER(Rays), i64, i64, vp]),
     "ot_rays_fill_sections": (C.c_int, [vp, vp, C.POINTER(SourceRange), i32, u64, C.POINTER(Rays), i64, i64, vp]),
+    "ot_scene_set_hot_steps": (C.c_int, [vp, i32]),
+    "ot_scene_read_hot_steps": (C.c_int, [vp, vp, i64, C.POINTER(i32)]),
+    "ot_scene_records_host": (C.c_int, [C.POINTER(SceneDesc), i32, i32, vp, i64, C.POINTER(i32), C.POINTER(i32)]),
     "ot_surface_find_hit": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp, vp, vp]),
     "ot_surface_normals": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp]),
     "ot_surface_mask": (C.c_int, [C.POINTER(Surface), i64, vp, vp, vp, vp]),
@@ -222,6 +225,7 @@ DET_MAX = 8  # OT_DET_MAX in csrc/ot_detector.hpp: detectors per call of ot_dete
 ABI_VERSION = 9  # OT_ABI_VERSION
 ERR_UNSUPPORTED = -3  # OT_ERR_UNSUPPORTED
 OT_DEFER_INDEX, OT_DEFER_POL, OT_DEFER_SECTIONS = 1, 2, 4  # ot_scene_set_deferred_planes
+HOT_OTHER, HOT_FLAT, HOT_RING, HOT_SPHERE, HOT_SPHERE_STABLE, HOT_CONIC = range(6)  # OT_HOT_* (csrc/ot_scene.hpp)
 SAMPLE_INTERVAL, SAMPLE_RECTANGLE, SAMPLE_RING = range(3)  # OT_SAMPLE_*
 SAMPLE_DISCRETE, SAMPLE_CONTINUOUS = range(2)
 SPOT_M, SPOT_MAX_RADII, SPOT_MAX_FREQ = 8, 65536, 4096  # OT_SPOT_*

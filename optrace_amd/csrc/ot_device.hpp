@@ -416,16 +416,18 @@ OT_DEV void handle_abnormal_f(SF& sf, const V3& p, const V3& s, V3& ph, bool& hi
 // (profiles/hit_step).  Flatter spheres, where that loss grows to 6e-10 mm at R = 1e7, take the stable roots with A = 1.
 // (D itself is the reference's: B B - C A still loses u |o|^2 / (2 D) for a start far from a
 // strongly curved surface, see hit_cases.py on `far`.)
-#define OT_PLAIN_SPHERE_R 4096.0  // mm
+// (OT_PLAIN_SPHERE_R: ot_scene.hpp, 4096 mm)
+// `sphere` (k == 0.0) and `plain` (sphere and |R| <= OT_PLAIN_SPHERE_R) are wave-uniform: scalar branches, not selects.  The
+// SurfDev path evaluates them here, per step; a hot record (ot_scene.hpp::HotStep, which carries the fields of the same
+// names) brings them as its form.
 template <class SF>
-OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) {
+OT_DEV void find_hit_conic_form(SF& sf, const bool sphere, const bool plain, const V3& p, const V3& s, V3& ph, bool& hit) {
     double ox = p.x - sf.px, oy = p.y - sf.py, oz = p.z - sf.pz;
-    const bool sphere = (sf.k == 0.0);  // wave-uniform: a scalar branch, not a select
     double ozk = oz * sf.k1;
     double B = s.x * ox + s.y * oy + s.z * (ozk - sf.inv_rho);
     double C = oy * oy + ox * ox + oz * (ozk - sf.two_inv_rho);
     double A = 1.0, D, t1, t2;
-    if (sphere && fabs(sf.inv_rho) <= OT_PLAIN_SPHERE_R) {  // wave-uniform; A = 1.0: C * 1.0 == C, x / 1.0 == x exactly
+    if (plain) {  // A = 1.0: C * 1.0 == C, x / 1.0 == x exactly
         D = ot_sqrt(B * B - C);
         t1 = -B - D;
         t2 = -B + D;
@@ -446,7 +448,8 @@ OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) 
     bool c2 = (sf.z_lo <= z2) && (z2 <= sf.z_hi) && (z2 >= z) && (t2 < t1);
     double t = (c1 && !c2) ? t1 : t2;
     ph = along(p, s, t);
-    hit = surf_mask<false>(sf, ph.x, ph.y);
+    const double dx = ph.x - sf.px, dy = ph.y - sf.py;  // surf_mask of a conic: the disc
+    hit = dx * dx + dy * dy <= sf.r_eps2;
     bool nh = !hit || !isfinite(D) || (!sphere && A == 0 && B == 0) || (ph.z < sf.z_lo) || (ph.z > sf.z_hi);
     if (nh) {
         double tnh = (sf.z_max - p.z) / s.z;
@@ -457,6 +460,12 @@ OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) 
         ph = p;
         hit = false;
     }
+}
+
+template <class SF>
+OT_DEV void find_hit_conic(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit) {
+    const bool sphere = (sf.k == 0.0);
+    find_hit_conic_form(sf, sphere, sphere && fabs(sf.inv_rho) <= OT_PLAIN_SPHERE_R, p, s, ph, hit);
 }
 
 // Surface.values of an AsphericSurface (surface.py:137-164 with aspheric_surface.py:51-65), the cost function of its hit
@@ -644,6 +653,48 @@ OT_DEV bool find_hit(SF& sf, const V3& p, const V3& s, V3& ph, bool& hit, bool& 
         handle_abnormal<LEVEL>(sf, p, s, ph, hit, pc);
     }
     return ok;
+}
+
+// ---- the hot forms of a step (ot_scene.hpp::HotStep): find_hit and surf_normal<INSIDE> for the surfaces whose path the
+// host has decided, reading the hot record `h` alone.  The same operations in the same order as the SurfDev path takes for
+// such a surface, so the same bits; `form` is wave-uniform and not OT_HOT_OTHER.
+template <class HS>
+OT_DEV void find_hit_hot(HS& h, const int form, const V3& p, const V3& s, V3& ph, bool& hit) {
+    if (form <= OT_HOT_RING) {  // find_hit's flat branch for a disc or a ring
+        const double t = ot_div(h.pz - p.z, s.z);
+        ph = along(p, s, t);
+        const double dx = ph.x - h.px, dy = ph.y - h.py;
+        const double r2 = dx * dx + dy * dy;
+        hit = r2 <= h.r_eps2;
+        if (form == OT_HOT_RING) hit = hit && (h.ri_eps2 <= r2);
+        const struct {
+            double z_beh, z_max;
+        } edge = {h.z_hi, h.z_max};  // (z_beh and z_hi are both z_max + N_EPS)
+        handle_abnormal_f(edge, p, s, ph, hit, ph.z - h.z_max);  // Surface.values of a flat surface is z_max
+        return;
+    }
+    find_hit_conic_form(h, form != OT_HOT_CONIC, form == OT_HOT_SPHERE, p, s, ph, hit);
+}
+
+// the normal at a hit point (x, y) of a hot form (surf_normal<INSIDE>)
+template <class HS>
+OT_DEV V3 hot_normal(HS& h, const int form, double x, double y) {
+    V3 n = {0.0, 0.0, 1.0};
+    if (form <= OT_HOT_RING) return n;
+    const double dx = x - h.px, dy = y - h.py;
+    if (form != OT_HOT_CONIC) {  // k == 0.0
+        n.x = h.nrho * dx;
+        n.y = h.nrho * dy;
+        n.z = ot_sqrt(1 - h.rho2 * (dx * dx) - h.rho2 * (dy * dy));
+        return n;
+    }
+    const double r2 = dx * dx + dy * dy;  // (see surf_normal)
+    const double q = ot_sqrt(1 - h.krho2 * r2);
+    const double iq = ot_rcp3(q);
+    n.x = ot_div_r(h.nrho * dx, q, iq);
+    n.y = ot_div_r(h.nrho * dy, q, iq);
+    n.z = ot_sqrt(1 - (n.x * n.x + n.y * n.y));
+    return n;
 }
 
 // RingSurface.hurb_props ring_surface.py:88-121, SlitSurface.hurb_props slit_surface.py:65-87

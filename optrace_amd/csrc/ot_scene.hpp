@@ -68,6 +68,38 @@ struct StepDev {
     double fsign;  // ideal lens: np.sign(f)        raytracer.py:755
 };
 
+// The hot record of a step: what the closed-form path of the step loop reads of StepDev and SurfDev, in the order it is
+// read, with the wave-uniform decisions of that path taken once on the host (`form`).  Three 64-byte lines, so that what a
+// block of the step reads lies side by side (the loop reads it field by field where it is used; the compiler merges
+// neighbours of one block into wider scalar loads):
+//   line 0  the step and the placement and disc mask of its surface (every hot form, ideal lenses)
+//   line 1  the conic hit search, the ring mask
+//   line 2  the conic normal, the ideal lens
+// Every field is a copy of the StepDev / SurfDev field of the same name and is filled whatever the form is (z_hi is z_beh
+// as well: both are z_max + N_EPS); a form is the host's evaluation of the comparisons the device code made per step:
+//   OT_HOT_OTHER          everything else -- rectangles, slits, tilted planes, aspheres, data surfaces, a conic record with
+//                         a flat sag -- reads SurfDev as before
+//   OT_HOT_FLAT, _RING    kind CIRCLE / RING and flat: plane hit, disc / ring mask, normal (0, 0, 1)
+//   OT_HOT_SPHERE         kind CONIC, not flat, k == 0.0 and fabs(inv_rho) <= OT_PLAIN_SPHERE_R: the reference's -B -+ D
+//   OT_HOT_SPHERE_STABLE  kind CONIC, not flat, k == 0.0, flatter: stable roots with A = 1
+//   OT_HOT_CONIC          kind CONIC, not flat, k != 0.0
+// The table holds n_steps + 1 records: the last one is zeroed padding (form OTHER), so the record after a step's may be
+// read before the loop knows whether that step exists.
+#define OT_HOT_OTHER 0
+#define OT_HOT_FLAT 1
+#define OT_HOT_RING 2
+#define OT_HOT_SPHERE 3
+#define OT_HOT_SPHERE_STABLE 4
+#define OT_HOT_CONIC 5
+#define OT_PLAIN_SPHERE_R 4096.0  // mm (ot_device.hpp::find_hit_conic)
+struct alignas(64) HotStep {
+    int32_t kind, form, surf, n_next, filter, hurb, hurb_slot, _pad0;
+    double px, py, pz, r_eps2;
+    double z_max, z_lo, z_hi, k1, inv_rho, two_inv_rho, k, ri_eps2;
+    double nrho, rho2, krho2, f, fsign, _pad[3];
+};
+static_assert(sizeof(HotStep) == 192, "HotStep is three 64-byte lines");
+
 struct FilterDev {
     int32_t type, inverse, tab_len, _pad;
     int64_t tab_off;
@@ -92,6 +124,7 @@ struct SceneDev {
     // (n_next, n1/n2, filter T) and finally the ambient row n0: doubles at line_tab[row * OT_MAX_LINES + j]
     int32_t n_lines, _pad2;
     const double* line_tab;
+    const HotStep* hot;  // n_steps + 1 records
 };
 
 struct ot_scene {
@@ -116,6 +149,10 @@ struct ot_scene {
     // SPEC of the last stored trace (0 formulas, 1 + tables, 2 per-line tables; -1: none yet): ot_rays_fill_index evaluates
     // the indices the way that launch did
     int index_spec = -1;
+    // ot_scene_set_hot_steps: the hot records as compiled (host copy) and whether the device table carries their forms
+    // (off: every record's form is OT_HOT_OTHER there, the fields stay)
+    HotStep* hot_host = nullptr;
+    bool hot_steps = true;
 };
 
 // ---- sources -------------------------------------------------------------------------------------------

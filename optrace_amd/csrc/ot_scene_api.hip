@@ -242,20 +242,9 @@ LeafSurface::~LeafSurface() {
     }
 }
 
-extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
-    if (!desc || !out) return fail(OT_ERR_INVALID, "ot_scene_create: null argument");
-    if (int rc = require_device()) return rc;
-    if (desc->n_elements < 1 || desc->n_surfaces < 1 || desc->n_media < 1)
-        return fail(OT_ERR_INVALID, "scene needs at least one element, surface and medium");
-    if (desc->n0 < 0 || desc->n0 >= desc->n_media) return fail(OT_ERR_INVALID, "scene: n0 out of range");
-
-    std::vector<SurfDev> surfs(desc->n_surfaces);
-    for (int i = 0; i < desc->n_surfaces; i++)
-        if (int rc = compile_surface(desc->surfaces[i], surfs[i])) return rc;
-
-    // flatten elements into one step per tracing surface
-    std::vector<StepDev> steps;
-    int n_hurb = 0;
+// flatten elements into one step per tracing surface
+static int compile_steps(const ot_scene_desc* desc, const std::vector<SurfDev>& surfs, std::vector<StepDev>& steps, int& n_hurb) {
+    n_hurb = 0;
     for (int i = 0; i < desc->n_elements; i++) {
         const ot_element& e = desc->elements[i];
         if (e.front < 0 || e.front >= desc->n_surfaces) return fail(OT_ERR_INVALID, "element: front surface out of range");
@@ -306,6 +295,55 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
                 return fail(OT_ERR_INVALID, "element: unknown kind");
         }
     }
+    return OT_OK;
+}
+
+static int hot_form(const SurfDev& sf) {
+    if (sf.kind == OT_SURF_CIRCLE && sf.flat) return OT_HOT_FLAT;
+    if (sf.kind == OT_SURF_RING && sf.flat) return OT_HOT_RING;
+    if (sf.kind != OT_SURF_CONIC || sf.flat) return OT_HOT_OTHER;
+    if (!(sf.k == 0.0)) return OT_HOT_CONIC;  // the comparisons of find_hit_conic and surf_normal, taken once
+    return std::fabs(sf.inv_rho) <= OT_PLAIN_SPHERE_R ? OT_HOT_SPHERE : OT_HOT_SPHERE_STABLE;
+}
+
+// the hot records of the steps (ot_scene.hpp::HotStep) and one record of padding; hot_steps == 0: every form is OTHER
+static void compile_hot_steps(const std::vector<StepDev>& steps, const std::vector<SurfDev>& surfs, bool hot_steps,
+                       std::vector<HotStep>& out) {
+    out.assign(steps.size() + 1, HotStep{});
+    for (size_t i = 0; i < steps.size(); i++) {
+        const StepDev& st = steps[i];
+        const SurfDev& sf = surfs[st.surf];
+        HotStep& h = out[i];
+        h.kind = st.kind;
+        h.form = hot_steps ? hot_form(sf) : OT_HOT_OTHER;
+        h.surf = st.surf;
+        h.n_next = st.n_next;
+        h.filter = st.filter;
+        h.hurb = st.hurb;
+        h.hurb_slot = st.hurb_slot;
+        h.px = sf.px, h.py = sf.py, h.pz = sf.pz, h.r_eps2 = sf.r_eps2;
+        h.z_max = sf.z_max, h.z_lo = sf.z_lo, h.z_hi = sf.z_hi, h.k1 = sf.k1;
+        h.inv_rho = sf.inv_rho, h.two_inv_rho = sf.two_inv_rho, h.k = sf.k, h.ri_eps2 = sf.ri_eps2;
+        h.nrho = sf.nrho, h.rho2 = sf.rho2, h.krho2 = sf.krho2, h.f = st.f, h.fsign = st.fsign;
+    }
+}
+
+extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
+    if (!desc || !out) return fail(OT_ERR_INVALID, "ot_scene_create: null argument");
+    if (int rc = require_device()) return rc;
+    if (desc->n_elements < 1 || desc->n_surfaces < 1 || desc->n_media < 1)
+        return fail(OT_ERR_INVALID, "scene needs at least one element, surface and medium");
+    if (desc->n0 < 0 || desc->n0 >= desc->n_media) return fail(OT_ERR_INVALID, "scene: n0 out of range");
+
+    std::vector<SurfDev> surfs(desc->n_surfaces);
+    for (int i = 0; i < desc->n_surfaces; i++)
+        if (int rc = compile_surface(desc->surfaces[i], surfs[i])) return rc;
+
+    std::vector<StepDev> steps;
+    int n_hurb = 0;
+    if (int rc = compile_steps(desc, surfs, steps, n_hurb)) return rc;
+    std::vector<HotStep> hot;
+    compile_hot_steps(steps, surfs, true, hot);
     bool needs_hurb = false, needs_ideal_filter = false;  // anything beyond lens surfaces and plain apertures
     int hit_level = OT_HIT_CLOSED;
     for (const StepDev& d : steps) {
@@ -394,7 +432,8 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
     size_t pool_n = desc->table_pool_len > 0 ? (size_t)desc->table_pool_len : 1;
     size_t o_lines = align_up(o_pool + sizeof(double) * pool_n);
     size_t o_cnt = align_up(o_lines + sizeof(double) * (line_tab.size() + 1));
-    size_t o_stab = align_up(o_cnt + sizeof(unsigned int) * (size_t)OT_CNT_SLOTS * (OT_N_INFOS * nt + 1));
+    size_t o_hot = (o_cnt + sizeof(unsigned int) * (size_t)OT_CNT_SLOTS * (OT_N_INFOS * nt + 1) + 63) / 64 * 64;
+    size_t o_stab = align_up(o_hot + sizeof(HotStep) * hot.size());
     std::vector<size_t> stab_off(surfs.size(), 0);  // spline tables of data surfaces, coefficients of long aspheres
     std::vector<DeviceTable> stabs;
     stabs.reserve(surfs.size());
@@ -432,6 +471,7 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
     h.pool_len = desc->table_pool_len;
     h.n_lines = n_lines;
     h.line_tab = (const double*)(blob + o_lines);
+    h.hot = (const HotStep*)(blob + o_hot);
 
     for (size_t i = 0; i < surfs.size(); i++) {
         if (!surfs[i].tab) continue;
@@ -446,6 +486,7 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
     if (desc->table_pool_len > 0)
         std::memcpy(host.data() + o_pool, desc->table_pool, sizeof(double) * desc->table_pool_len);
     if (!line_tab.empty()) std::memcpy(host.data() + o_lines, line_tab.data(), sizeof(double) * line_tab.size());
+    std::memcpy(host.data() + o_hot, hot.data(), sizeof(HotStep) * hot.size());
     hipError_t e = hipMemcpy(blob, host.data(), total, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(blob);
@@ -461,6 +502,8 @@ extern "C" int ot_scene_create(const ot_scene_desc* desc, ot_scene** out) {
     sc->hit_level = hit_level;
     sc->d = (SceneDev*)(blob + o_hdr);
     sc->blob = blob;
+    sc->hot_host = new HotStep[hot.size()];
+    std::memcpy(sc->hot_host, hot.data(), sizeof(HotStep) * hot.size());
     (void)hipGetDevice(&sc->device);
     *out = sc;
     return OT_OK;
@@ -472,6 +515,7 @@ extern "C" void ot_scene_destroy(ot_scene* sc) {
     if (sc->pin_msgs) (void)hipHostFree(sc->pin_msgs);
     if (sc->ev0) (void)hipEventDestroy(sc->ev0);
     if (sc->ev1) (void)hipEventDestroy(sc->ev1);
+    delete[] sc->hot_host;
     delete sc;
 }
 
@@ -503,6 +547,75 @@ extern "C" int ot_scene_set_deferred_planes(ot_scene* sc, uint32_t mask) {
 extern "C" int ot_scene_set_index_store(ot_scene* sc, int32_t on) {
     if (!sc) return fail(OT_ERR_INVALID, "ot_scene_set_index_store: null scene");
     return ot_scene_set_deferred_planes(sc, on ? 0u : (sc->deferred | OT_DEFER_INDEX));
+}
+
+// The hot records of the step loop (ot_scene.hpp::HotStep) with their forms (on, the default) or with every form OTHER, so
+// that every step reads its SurfDev record: the same kernel either way, for comparing the two paths.  Rewrites the device
+// table on the scene's own device, whichever device is current; launches already queued there are waited for first.
+namespace {
+struct SceneDevice {  // the scene's device for the length of a call
+    int before = -1;
+    explicit SceneDevice(const ot_scene* sc) {
+        if (hipGetDevice(&before) != hipSuccess || before == sc->device || hipSetDevice(sc->device) != hipSuccess) before = -1;
+    }
+    ~SceneDevice() {
+        if (before >= 0) (void)hipSetDevice(before);
+    }
+};
+}  // namespace
+
+extern "C" int ot_scene_set_hot_steps(ot_scene* sc, int32_t on) {
+    if (!sc) return fail(OT_ERR_INVALID, "ot_scene_set_hot_steps: null scene");
+    if ((on != 0) == sc->hot_steps) return OT_OK;
+    const size_t n = (size_t)sc->h.n_steps + 1;
+    std::vector<HotStep> tab(sc->hot_host, sc->hot_host + n);
+    if (!on)
+        for (HotStep& h : tab) h.form = OT_HOT_OTHER;
+    const SceneDevice on_device(sc);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(const_cast<HotStep*>(sc->h.hot), tab.data(), sizeof(HotStep) * n, hipMemcpyHostToDevice));
+    sc->hot_steps = on != 0;
+    return OT_OK;
+}
+
+// the hot records as the device holds them now (n_steps + 1 records of sizeof(HotStep)), for checks of the switch above
+extern "C" int ot_scene_read_hot_steps(const ot_scene* sc, void* buf, int64_t buf_bytes, int32_t* count) {
+    if (!sc || !buf || !count) return fail(OT_ERR_INVALID, "ot_scene_read_hot_steps: null argument");
+    const size_t n = (size_t)sc->h.n_steps + 1;
+    *count = (int32_t)n;
+    if (buf_bytes < (int64_t)(n * sizeof(HotStep))) return fail(OT_ERR_INVALID, "ot_scene_read_hot_steps: buffer too small");
+    const SceneDevice on_device(sc);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(buf, sc->h.hot, sizeof(HotStep) * n, hipMemcpyDeviceToHost));
+    return OT_OK;
+}
+
+// Host only, no device: the records ot_scene_create compiles from a scene description, copied into the caller's buffer.
+// table 0: the hot records (n_steps + 1, the last one padding; hot_steps as for ot_scene_set_hot_steps), 1: the surface
+// records (SurfDev; table pointers are the description's host pointers), 2: the step records (StepDev).  `count` and
+// `record_bytes` receive the number of records and the size of one; a null buffer asks for those alone.
+extern "C" int ot_scene_records_host(const ot_scene_desc* desc, int32_t table, int32_t hot_steps, void* buf, int64_t buf_bytes,
+                                     int32_t* count, int32_t* record_bytes) {
+    if (!desc || !count || !record_bytes) return fail(OT_ERR_INVALID, "ot_scene_records_host: null argument");
+    if (table < 0 || table > 2) return fail(OT_ERR_INVALID, "ot_scene_records_host: table must be 0, 1 or 2");
+    if (desc->n_elements < 1 || desc->n_surfaces < 1) return fail(OT_ERR_INVALID, "scene needs at least one element, surface and medium");
+    std::vector<SurfDev> surfs(desc->n_surfaces);
+    for (int i = 0; i < desc->n_surfaces; i++)
+        if (int rc = compile_surface(desc->surfaces[i], surfs[i])) return rc;
+    std::vector<StepDev> steps;
+    int n_hurb = 0;
+    if (int rc = compile_steps(desc, surfs, steps, n_hurb)) return rc;
+    std::vector<HotStep> hot;
+    compile_hot_steps(steps, surfs, hot_steps != 0, hot);
+    const void* src = table == 0 ? (const void*)hot.data() : table == 1 ? (const void*)surfs.data() : (const void*)steps.data();
+    const size_t n = table == 0 ? hot.size() : table == 1 ? surfs.size() : steps.size();
+    const size_t one = table == 0 ? sizeof(HotStep) : table == 1 ? sizeof(SurfDev) : sizeof(StepDev);
+    *count = (int32_t)n;
+    *record_bytes = (int32_t)one;
+    if (!buf) return OT_OK;
+    if (buf_bytes < (int64_t)(n * one)) return fail(OT_ERR_INVALID, "ot_scene_records_host: buffer too small");
+    std::memcpy(buf, src, n * one);
+    return OT_OK;
 }
 
 extern "C" int ot_scene_last_trace_ms(const ot_scene* sc, double* ms) {

@@ -214,11 +214,9 @@ OT_DEV double fresnel_T2(double n1, double n2, double ns, double W, double A_ts2
 
 // Raytracer.__refraction raytracer.py:761-829 for a lane that has power and hit the surface.
 // The new direction s' is computed in the reference's exact operation order (it feeds the next hit mask).
-// Returns true on total internal reflection.
-template <bool POL, int LEVEL, class SF>
-OT_DEV bool refract(SF& sf, RayState& r, const V3& pn, float& wn, float& npx, float& npy, float& npz,
-                    double n1, double n2, double N, PatchCache* pc = nullptr) {  // N = n1 / n2 (raytracer.py:799)
-    V3 n = surf_normal<true, LEVEL>(sf, pn.x, pn.y, pc);  // pn is a hit point: is_hit implies mask(pn) (surface.py:409)
+// `n` is the surface normal at the hit point, N = n1 / n2 (raytracer.py:799).  Returns true on total internal reflection.
+template <bool POL>
+OT_DEV bool refract(const V3& n, RayState& r, float& wn, float& npx, float& npy, float& npz, double n1, double n2, double N) {
     V3 s = r.s;
     double ns = dot3(n, s);
     double W = ot_sqrt(1 - N * N * (1 - ns * ns));
@@ -476,7 +474,7 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
     PatchCache* const pc = SPLINE ? &pcache : nullptr;
     const int nt = sc.nt;
     const auto surfaces = as_const(sc.surfaces);
-    const auto steps = as_const(sc.steps);
+    const auto hot = as_const(sc.hot);
     const auto media = as_const(sc.media);
     const auto filters = as_const(sc.filters);
     const auto pool = as_const(sc.pool);
@@ -494,7 +492,10 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
 #endif
 
     for (int i = 0; i < sc.n_steps; i++) {  // i = index of the section the ray starts this step in
-        auto& st = steps[i];
+        // The step's hot record (ot_scene.hpp::HotStep): what a block of the step reads lies side by side in it, and `form`
+        // says whether the record is all the step needs or the surface record is read as well.
+        auto& st = hot[i];
+        const int form = st.form;
         if (TAIL && i + 1 == sc.n_steps) {  // the last section starts here
             tail->p = r.p;
             tail->w = r.w;
@@ -511,7 +512,10 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
             pcache.key = nullptr;
         }
         if (hw) {
-            ok &= find_hit<LEVEL>(sf, r.p, r.s, ph, hit, ill, pc);
+            if (form != OT_HOT_OTHER)
+                find_hit_hot(st, form, r.p, r.s, ph, hit);
+            else
+                ok &= find_hit<LEVEL>(sf, r.p, r.s, ph, hit, ill, pc);
             pn = ph;
         }
         if (NUMERIC) count_event(msgs, nt, OT_INFO_ILL_COND, i + 1, hw && ill);
@@ -533,10 +537,17 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
                 Nq = ot_div(r.n_cur, n_next);
             }
             if (hwh) {
-                if (IDEAL_FILTER && kind == OT_STEP_IDEAL)
-                    refract_ideal<POL>(sf, st, r, pn, npx, npy, npz);
-                else
-                    tir = refract<POL, LEVEL>(sf, r, pn, wn, npx, npy, npz, r.n_cur, n_next, Nq, pc);
+                if (IDEAL_FILTER && kind == OT_STEP_IDEAL) {
+                    refract_ideal<POL>(st, st, r, pn, npx, npy, npz);
+                } else {
+                    // pn is a hit point: is_hit implies mask(pn) (surface.py:409)
+                    V3 n;
+                    if (form != OT_HOT_OTHER)
+                        n = hot_normal(st, form, pn.x, pn.y);
+                    else
+                        n = surf_normal<true, LEVEL>(sf, pn.x, pn.y, pc);
+                    tir = refract<POL>(n, r, wn, npx, npy, npz, r.n_cur, n_next, Nq);
+                }
             }
         } else if (IDEAL_FILTER && kind == OT_STEP_FILTER) {  // raytracer.py:379-380
             if (hwh) {

@@ -48,6 +48,11 @@
                  : ((FEAT) == 1 ? OT_TRACE_MIN_WAVES_F1                                                    \
                                 : ((FEAT) == 3 ? OT_TRACE_MIN_WAVES_F3 : ((FEAT) == 4 ? OT_TRACE_MIN_WAVES_F4 : OT_TRACE_MIN_WAVES))))
 
+// the storing form: level 0 with polarisation on rays handed in takes 80 registers when asked for six waves and 81 -- five
+// waves -- when not (profiles/r8/resource_usage.txt)
+#define OT_TRACE_WAVES_STORE(FEAT, SPEC, POL, GEN) \
+    (((FEAT) == 0 && (POL) && !(GEN)) ? OT_TRACE_MIN_WAVES_F0_LINES : OT_TRACE_WAVES(FEAT, SPEC, POL))
+
 struct RangeRec {  // one source range in device memory (scenes with more than OT_MAX_RANGES ranges)
     int64_t first, count;
     int32_t source;
@@ -241,7 +246,8 @@ OT_DEV void flush_counters(TraceLds f, unsigned int* slots) {
 // [sec_first, sec_end): the sections whose position and weight planes this launch writes (ot_trace.hpp::store_section_next) --
 // all of them, the last two (OT_DEFER_SECTIONS) or all but those (ot_rays_fill_sections); kernel arguments, so wave-uniform.
 template <bool POL, bool GEN, int SPEC, int FEAT>
-__global__ __launch_bounds__(256, OT_TRACE_WAVES(FEAT, SPEC, POL)) void trace_kernel(const SceneDev* __restrict__ scp, ot_rays R,
+__global__ __launch_bounds__(256, OT_TRACE_WAVES_STORE(FEAT, SPEC, POL, GEN))
+void trace_kernel(const SceneDev* __restrict__ scp, ot_rays R,
                                                     const SourceDev* __restrict__ sources, RangeArgs rg,
                                                     const double* __restrict__ hurb_normals, uint64_t seed,
                                                     unsigned int* __restrict__ slots, int64_t ray_base,
