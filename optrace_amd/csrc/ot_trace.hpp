@@ -100,79 +100,81 @@ OT_DEV double fast_rcp(double x) {
     return y;
 }
 
-// Fresnel power transmission raytracer.py:813-819, algebraically regrouped to a single division:
-//   T = n2cb/n1ca * ((A_ts*ts)^2 + (A_tp*tp)^2),  ts = 2 n1ca/d1,  tp = 2 n1ca/d2
-//     = 4 n1ca n2cb (A_ts^2 d2^2 + A_tp^2 d1^2) / (d1 d2)^2
-// (feeds only the float32 weight; see compute_polarization for the tolerance argument)
-OT_DEV double fresnel_T(double n1, double n2, double ns, double W, double A_ts, double A_tp) {
-#pragma clang fp contract(fast)
-    double n1ca = n1 * ns, n2cb = n2 * W;
-    double d1 = n1ca + n2cb;
-    double d2 = n2 * ns + n1 * W;
-    double a = A_ts * d2, b = A_tp * d1;
-    double den = d1 * d2;
-    double T = 4 * n1ca * n2cb * (a * a + b * b) * fast_rcp(den * den);
-    if (n1ca == 0) T = __builtin_nan("");  // the reference divides by n1*cos(alpha)
-    return T;
-}
+// |n x s|^2 below which refraction_polarization drops the plane-of-incidence term of pol', i.e. sin(alpha) = 2^-26: where
+// the form's rounding error (~3 * 2^-53 / sin(alpha)) meets the size of the dropped term (<= sin(alpha)).  From a host sweep
+// of the float64 restatement against exact values (tests/pol_form.py; 2160 rays, sin(alpha) = 2^-30 .. 2^-20, three
+// normals, six pairs of media), largest error of pol' before the float32 store in units of the noise part of the bar of
+// tests/test_gpu_refraction_step.py (2^-30 + min(2^-25, 2^-49 / sin(alpha))), per threshold:
+//     2^-56: 1.47    2^-54: 0.68    2^-53: 0.48    2^-52: 0.46    2^-51: 0.53    2^-50: 0.75    2^-49: 1.10    2^-48: 1.69
+// (worst case at 2^-52: sin(alpha) = 2^-25.95 on the flat normal, n = 1.5015 -> 1.5, i.e. the form just above the
+// threshold).  The weights use 2e-7 of theirs at every threshold.
+#ifndef OT_POL_NEAR
+#define OT_POL_NEAR 0x1p-52
+#endif
 
-// __compute_polarization specialised for refraction, where s' = N s - q n lies in the plane of n and s.
+// __compute_polarization and the Fresnel factor for refraction, where s' = N s - q n lies in the plane of n and s.
 // With m = n x s (|m| = sin(alpha)) the reference's basis vectors are, by (a x b) x c = b (a.c) - a (b.c):
 //     ps  = +-m / |m|                      (the sign cancels in A_ts ps and in A_ts^2)
 //     pp  = ps x s  = (ns s - n) / |m|
-//     pp' = ps x s' = (W s - (s.s') n) / |m|,      n.s' = W,   s.s' = N - q ns
-// so   A_ts = (m.pol)/|m|,  A_tp = (ns (s.pol) - n.pol)/|m|,  pol' = [(m.pol) m + A_tp|m| (W s - (s.s') n)] / |m|^2.
-// No identity relies on pol being exactly perpendicular to s (the float32-stored pol is not; see above why that
-// matters), so this agrees with the reference's projection to rounding, with one cross product instead of three
-// and a reciprocal instead of a reciprocal square root (~66 instead of ~83 instructions).
-template <bool POL>
-OT_DEV void refraction_polarization(const V3& n, const V3& s, const V3& s_, double ns, double W, double N, double q,
-                                    const RayState& r, float& npx, float& npy, float& npz, double& A_ts2, double& A_tp2) {
-#pragma clang fp contract(fast)
-    if (!POL) {  // (1/np.sqrt(2))**2 each
-        A_ts2 = 0.5;
-        A_tp2 = 0.5;
-        return;
-    }
+//     pp' = ps x s' = (W s - (s.s') n) / |m|,      n.s' = W,   s.s' = ct = N - q ns
+// so   A_ts = (m.pol)/|m|,  A_tp = tp/|m| with tp = ns (s.pol) - n.pol,  pol' = [(m.pol) m + tp (W s - ct n)] / |m|^2.
+// The cross product itself is not needed: {m/|m|, s, e/|m|} with e = n - ns s is an orthonormal frame for unit n and s,
+// e.pol = -tp, so the part of pol along m is pol minus its parts along s and e, for ANY pol:
+//     (m.pol) m / mm = pol - (s.pol) s + tp e / mm,        (m.pol)^2 / mm = |pol|^2 - (s.pol)^2 - tp^2 / mm,     mm = e.e
+//     pol'   = pol - (s.pol) s + (tp / mm) [(W - ns) s + (1 - ct) n]
+//     A_tp^2 = tp^2 / mm,       A_ts^2 = P - A_tp^2,       P = |pol|^2 - (s.pol)^2
+// No identity relies on pol being exactly perpendicular to s (the float32-stored pol is not; see above why that matters):
+// this is the reference's projection to rounding, without a cross product, m.pol or the vector W s - ct n.  mm is e.e,
+// which is conditioned like |n x s|^2 and formed from the same n and s as tp, so that tp^2 <= P mm holds to rounding even
+// where n is unit only to a few ulps; 1 - ns^2 (three instructions cheaper) has neither property, although the host sweep
+// could not tell the two apart by the bars (tests/test_pol_form_host.py).
+// The Fresnel factor is closed by refract, which wants the squared amplitudes as A = (A_ts^2 + A_tp^2) M, B = A_tp^2 M
+// over a common denominator M: here A = P mm, B = tp^2, M = mm, so that one reciprocal serves T and the 1 / mm of pol'.
+// The split between the two amplitudes only enters T through d1^2 - d2^2 = O(sin^2), which cancels its conditioning.
+// The products are fused by hand: the file is compiled without contraction, and a pragma does not reach into helpers
+// defined elsewhere (dot3 and cross3 of ot_device.hpp came out unfused under `fp contract(fast)`).
+// Returns whether pol changes: then pol' = pol - sp s + (tp / M) [...], which refract forms once it has 1 / M.
+OT_DEV bool refraction_polarization(const V3& n, const V3& s, const V3& s_, double ns, const RayState& r, double& A,
+                                    double& B, double& M, double& tp, double& sp) {
+    const V3 pol = {(double)r.polx, (double)r.poly, (double)r.polz};
+    sp = __builtin_fma(s.z, pol.z, __builtin_fma(s.y, pol.y, s.x * pol.x));
+    const double np_ = __builtin_fma(n.z, pol.z, __builtin_fma(n.y, pol.y, n.x * pol.x));
+    const double P = __builtin_fma(-sp, sp, __builtin_fma(pol.z, pol.z, __builtin_fma(pol.y, pol.y, pol.x * pol.x)));
+    tp = __builtin_fma(ns, sp, -np_);  // A_tp |m|
+    const V3 e = {__builtin_fma(-ns, s.x, n.x), __builtin_fma(-ns, s.y, n.y), __builtin_fma(-ns, s.z, n.z)};
+    M = __builtin_fma(e.z, e.z, __builtin_fma(e.y, e.y, e.x * e.x));
+    A = P * M;
+    B = tp * tp;
     bool mask = (s.x != s_.x) || (s.y != s_.y) || (s.z != s_.z);
-    V3 m = cross3(n, s);
-    V3 pol = {(double)r.polx, (double)r.poly, (double)r.polz};
-    double mm = dot3(m, m), mp = dot3(m, pol), sp = dot3(s, pol), np_ = dot3(n, pol);
-    // n and s exactly parallel (a collimated beam along a face normal) while s' still differs from s by rounding:
-    // the plane of incidence is undefined (m = 0, 1 / mm not finite).  The reference builds its basis from the
-    // rounding noise s' x s: it loses up to 2e-3 of the weight that way, or divides 0 by 0 where the noise cancels
-    // (tests/test_refraction_host.py).  The limit is the normal-incidence transmission (ts = tp) and an unchanged pol
-    // -- which is the unchanged-direction branch.
-    // Nearly parallel as well: mp and tp each carry an absolute rounding error of ~2^-53 against a magnitude of |m|, so
-    // below |m| ~ 2^-25 their squares over mm stop adding up to |pol_perp|^2 (on a tilted normal at |m| = 2^-48 the weight
-    // was off by 4 % and could exceed the incoming one).  There ts = tp to |m|^2 and pol' = pol to |m|: the split between
-    // the two amplitudes does not matter, their sum |pol|^2 - (s.pol)^2 does -- the float32 pol is unit only to 1e-7.
-    // 2^-54: at |m| = 2^-27 both forms are good to 2^-26 relative, below the float32 store.  m == 0 keeps 1/2 + 1/2, the
-    // reference's contract for an unchanged direction.  One comparison on the common path (it replaces mm > 0); the rest
-    // sits behind a wave-uniform branch that the waves of an ordinary bundle skip.
-    const bool near = !(mm >= 0x1p-54);  // m == 0 and NaN included
-    double half = 0.5;
-    if (__ballot(near) != 0ull) {
-        if (near) {
-            mask = false;
-            if (mm > 0) half = 0.5 * (dot3(pol, pol) - sp * sp);
+    // Nearly parallel n and s: tp and e each carry an absolute rounding error of ~2^-53 against a magnitude of |m|, so the
+    // term (tp / mm) [...] of pol', of size ~|m|, is off by ~3 * 2^-53 / |m|, and below |m| ~ 2^-26 it is noise (on a
+    // tilted normal at |m| = 2^-48 a basis made there put the weight off by 4 %).  Dropping it costs at most its size:
+    // there pol' = pol - (s.pol) s, ts = tp to |m|^2, and only the sum of the two squared amplitudes, P, matters -- the
+    // float32 pol is unit only to 1e-7 -- split evenly.  The threshold: OT_POL_NEAR.
+    // n x s == 0 exactly (a collimated beam along a face normal; s' may still differ from s by a rounding, and the
+    // reference then builds its basis from the rounding noise s' x s, loses up to 2e-3 of the weight or divides 0 by 0,
+    // tests/test_refraction_host.py) and s' == s bitwise keep pol and 1/2 + 1/2, the reference's contract for an
+    // unchanged direction.  e does not tell: for s == n it is n (1 - n.n), a few ulps and not zero, so the exact cross
+    // product is formed here, behind a wave-uniform branch that the waves of an ordinary bundle skip.  One comparison
+    // more than the mask on the common path; a ballot per comparison, because each is then that comparison's own lane
+    // mask (the ballot of a combined condition costs two vector instructions to form it).
+    const bool near = !(M >= OT_POL_NEAR);  // NaN included
+    const unsigned long long moved = __ballot(s.x != s_.x) | __ballot(s.y != s_.y) | __ballot(s.z != s_.z);
+    if (__ballot(near) != 0ull || moved != __ballot(true)) {
+        if (near || !mask) {
+            const V3 m = cross3(n, s);
+            double half = 0.5 * P;
+            if (!mask || !(dot3(m, m) > 0)) {
+                mask = false;
+                half = 0.5;
+            }
+            A = 2 * half;
+            B = half;
+            M = 1;
+            tp = 0;
         }
     }
-    double inv = fast_rcp(mm);
-    double tp = ns * sp - np_;   // A_tp |m|
-    double ct = N - q * ns;      // s . s'
-    A_ts2 = mp * mp * inv;
-    A_tp2 = tp * tp * inv;
-    if (!mask) {
-        A_ts2 = half;
-        A_tp2 = half;
-    }
-    if (mask) {
-        V3 vec = {W * s.x - ct * n.x, W * s.y - ct * n.y, W * s.z - ct * n.z};
-        npx = (float)((mp * m.x + tp * vec.x) * inv);
-        npy = (float)((mp * m.y + tp * vec.y) * inv);
-        npz = (float)((mp * m.z + tp * vec.z) * inv);
-    }
+    return mask;
 }
 
 // __compute_polarization for a surface with the same medium on both sides (N == 1, e.g. a lens whose n2 is its own n).
@@ -200,36 +202,58 @@ OT_DEV void same_medium_polarization(const V3& s, const V3& s_, const RayState& 
     }
 }
 
-// Fresnel power transmission from squared amplitudes (see fresnel_T)
-OT_DEV double fresnel_T2(double n1, double n2, double ns, double W, double A_ts2, double A_tp2) {
-#pragma clang fp contract(fast)
-    double n1ca = n1 * ns, n2cb = n2 * W;
-    double d1 = n1ca + n2cb;
-    double d2 = n2 * ns + n1 * W;
-    double den = d1 * d2;
-    double T = 4 * n1ca * n2cb * (A_ts2 * (d2 * d2) + A_tp2 * (d1 * d1)) * fast_rcp(den * den);
-    if (n1ca == 0) T = __builtin_nan("");  // the reference divides by n1*cos(alpha)
-    return T;
-}
-
 // Raytracer.__refraction raytracer.py:761-829 for a lane that has power and hit the surface.
 // The new direction s' is computed in the reference's exact operation order (it feeds the next hit mask).
 // `n` is the surface normal at the hit point, N = n1 / n2 (raytracer.py:799).  Returns true on total internal reflection.
+// npx, npy, npz hold the lane's pol on entry and pol' on return.
+//
+// Fresnel power transmission raytracer.py:813-819 from squared amplitudes, regrouped to a single division and divided
+// through by n2 (Nns = N ns is there for q anyway; n1 and n2 themselves are not needed):
+//   T = n2cb/n1ca * ((A_ts*ts)^2 + (A_tp*tp)^2),  ts = 2 n1ca/(n1ca + n2cb),  tp = 2 n1ca/(n2 ns + n1 W)
+//     = 4 Nns W (A_ts^2 d2^2 + A_tp^2 d1^2) / (d1 d2)^2,      d1 = Nns + W,  d2 = ns + N W
+//     = 4 Nns W (A d2^2 + B (d1^2 - d2^2)) / (M (d1 d2)^2),   A = (A_ts^2 + A_tp^2) M,  B = A_tp^2 M
+// (feeds only the float32 weight; see compute_polarization for the tolerance argument).  M is 1 except where
+// refraction_polarization hands over its own denominator.
 template <bool POL>
-OT_DEV bool refract(const V3& n, RayState& r, float& wn, float& npx, float& npy, float& npz, double n1, double n2, double N) {
+OT_DEV bool refract(const V3& n, RayState& r, float& wn, float& npx, float& npy, float& npz, double N) {
     V3 s = r.s;
     double ns = dot3(n, s);
     double W = ot_sqrt(1 - N * N * (1 - ns * ns));
-    double q = N * ns - W;
+    double Nns = N * ns;
+    double q = Nns - W;
     V3 s_ = {s.x * N - n.x * q, s.y * N - n.y * q, s.z * N - n.z * q};
 
-    double A_ts2, A_tp2;
-    if (POL && N == 1.0)
-        same_medium_polarization(s, s_, r, npx, npy, npz, A_ts2, A_tp2);
-    else
-        refraction_polarization<POL>(n, s, s_, ns, W, N, q, r, npx, npy, npz, A_ts2, A_tp2);
-    double T = fresnel_T2(n1, n2, ns, W, A_ts2, A_tp2);
-    bool tir = !isfinite(W);
+    double A = 1, B = 0.5, M = 1, tp, sp;  // A_ts^2 = A_tp^2 = (1/np.sqrt(2))**2
+    bool bend = false;
+    if (POL) {
+        if (N == 1.0) {
+            double A_ts2, A_tp2;
+            same_medium_polarization(s, s_, r, npx, npy, npz, A_ts2, A_tp2);
+            A = A_ts2 + A_tp2;
+            B = A_tp2;
+        } else {
+            bend = refraction_polarization(n, s, s_, ns, r, A, B, M, tp, sp);
+        }
+    }
+    // (the Fresnel terms are formed after the polarisation, not before: carried across it they cost the kernel its
+    // sixth wave's registers)
+    const double d1 = Nns + W, d2 = __builtin_fma(N, W, ns), den = d1 * d2;
+    const double d2s = d2 * d2, den2 = den * den;
+    const double rr = fast_rcp(M * den2);
+    double T = 4 * (Nns * W) * (__builtin_fma(A, d2s, B * __builtin_fma(d1, d1, -d2s)) * rr);
+    if (Nns == 0) T = __builtin_nan("");  // the reference divides by n1*cos(alpha)
+    if (POL && bend) {
+        const double k = tp * (rr * den2);  // tp / mm
+        const double g = k * (1 - __builtin_fma(-q, ns, N)), h = __builtin_fma(k, W - ns, -sp);  // 1 - s.s', n.s' - n.s
+        // pol is converted from its floats a second time: the empty statement hides from the compiler that it has the
+        // three doubles already, which it would otherwise keep in six registers from refraction_polarization to here
+        // (80 VGPRs and a spill in the bench kernel against 76 this way)
+        asm("" : "+v"(npx), "+v"(npy), "+v"(npz));
+        npx = (float)__builtin_fma(g, n.x, __builtin_fma(h, s.x, (double)npx));
+        npy = (float)__builtin_fma(g, n.y, __builtin_fma(h, s.y, (double)npy));
+        npz = (float)__builtin_fma(g, n.z, __builtin_fma(h, s.z, (double)npz));
+    }
+    const bool tir = !isfinite(W);
     if (tir) T = 0;
     wn = (float)((double)r.w * T);
     r.s = s_;
@@ -546,7 +570,7 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
                         n = hot_normal(st, form, pn.x, pn.y);
                     else
                         n = surf_normal<true, LEVEL>(sf, pn.x, pn.y, pc);
-                    tir = refract<POL>(n, r, wn, npx, npy, npz, r.n_cur, n_next, Nq);
+                    tir = refract<POL>(n, r, wn, npx, npy, npz, Nq);
                 }
             }
         } else if (IDEAL_FILTER && kind == OT_STEP_FILTER) {  // raytracer.py:379-380
