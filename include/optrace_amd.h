@@ -947,6 +947,10 @@ int ot_sample_srgb_wavelengths(const double* rgb, int64_t n, const ot_source_ran
  *   op:    0 ot_div(a, b) | 1 ot_sqrt(|a|) | 2 normalize3(a, b, c) | 3 two quotients a / c, b / c sharing one reciprocal
  *   class: 0 uniform mantissas, exponents +-500 (sqrt: 2^-760 .. 2^1020, normalize3: +-250) | 1 mm geometry 2^-20 .. 2^14
  *          | 2 refractive indices [1, 2.5] | 3 direction cosines near 0 and near 1
+ * op 4 with class 4 is a measurement instead: the relative error |1 - a y| of y = the hardware reciprocal seed, the seed
+ * with one and with two Newton steps, and the fast reciprocal the refraction step uses, over n operands a of the range that
+ * step produces (positive, exponents +-60).  first_bad4 receives the four largest errors in that order; mismatches counts
+ * the operands on which the shipped reciprocal exceeds the bound stated at its definition (csrc/ot_device.hpp).
  * ot_selftest_eval evaluates both on caller-supplied DEVICE operands (special values); outputs are (n, 3) F-order. */
 int ot_selftest_arith(int32_t op, int32_t operand_class, int64_t n, uint64_t seed, int64_t* mismatches,
                       double* first_bad4, void* stream);

@@ -99,7 +99,9 @@ int cu_count() {
 extern "C" int ot_selftest_arith(int32_t op, int32_t operand_class, int64_t n, uint64_t seed, int64_t* mismatches,
                                  double* first_bad4, void* stream) {
     if (!mismatches || !first_bad4 || n < 0) return fail(OT_ERR_INVALID, "ot_selftest_arith: bad argument");
-    if (op < OT_ST_DIV || op > OT_ST_DIV_SHARED || operand_class < OT_CLS_WIDE || operand_class > OT_CLS_COSINE)
+    // (the accuracy case and its operand class belong to each other)
+    if (op < OT_ST_DIV || op > OT_ST_FAST_RCP || operand_class < OT_CLS_WIDE || operand_class > OT_CLS_RECIPROCAL ||
+        (op == OT_ST_FAST_RCP) != (operand_class == OT_CLS_RECIPROCAL))
         return fail(OT_ERR_INVALID, "ot_selftest_arith: unknown operation or operand class");
     if (int rc = require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -108,7 +110,11 @@ extern "C" int ot_selftest_arith(int32_t op, int32_t operand_class, int64_t n, u
     hipError_t e = hipMemsetAsync(scratch, 0, 64, st);
     unsigned long long host[2] = {0, 0};
     double bad[4] = {0, 0, 0, 0};
-    if (e == hipSuccess && n > 0) {
+    if (e == hipSuccess && n > 0 && op == OT_ST_FAST_RCP) {
+        hipLaunchKernelGGL(selftest_rcp_kernel, dim3((unsigned)(cu_count() * 8)), dim3(256), 0, st, n, seed,
+                           (unsigned long long*)scratch, (double*)(scratch + 16));
+        e = hipGetLastError();
+    } else if (e == hipSuccess && n > 0) {
         hipLaunchKernelGGL(selftest_arith_kernel, dim3((unsigned)(cu_count() * 8)), dim3(256), 0, st, (int)op,
                            (int)operand_class, n, seed, (unsigned long long*)scratch, (double*)(scratch + 16));
         e = hipGetLastError();

@@ -71,6 +71,27 @@ OT_DEV double ot_div_r(double n, double d, double r) {  // r = ot_rcp3(d)
     return __builtin_fma(__builtin_fma(-d, q, n), r, q);
 }
 
+// 1 / x from the hardware seed (v_rcp_f64) and STEPS Newton steps y <- y + y (1 - x y), each squaring the relative error and
+// adding a rounding of its own.
+template <int STEPS>
+OT_DEV double rcp_newton(double x) {
+    double y = __builtin_amdgcn_rcp(x);
+#pragma unroll
+    for (int k = 0; k < STEPS; k++) y = fma(fma(-x, y, 1.0), y, y);
+    return y;
+}
+// 1 / x where the result ends up in a float32 only (refract: the Fresnel factor of the weight, the 1 / mm of pol'): the seed
+// and ONE Newton step.  Measured on the device by the library's self-test (ot_selftest.hpp, OT_ST_FAST_RCP: the largest
+// |1 - x y| over 2^27 operands of the range refract produces, positive with exponents within +-60; MI355X):
+//     v_rcp_f64 seed   2^-24.36        one step   2^-48.67        two steps   2^-53.00
+// (the seed is not the "~2^-26" this comment used to recall).  One step is 2^24 inside the rounding of the float32 the
+// result ends in, which is the bar set for dropping the second (at most 2^-48); tests/test_gpu_trace_loop.py asserts
+// OT_FAST_RCP_BOUND on the device for whatever OT_FAST_RCP_STEPS says.  ot_rcp3 above keeps both steps: positions and masks
+// rest on it.
+#define OT_FAST_RCP_STEPS 1
+#define OT_FAST_RCP_BOUND 0x1p-48
+OT_DEV double fast_rcp(double x) { return rcp_newton<OT_FAST_RCP_STEPS>(x); }
+
 // 1 / sqrt(x) for the generator's unit vectors (nothing the hit masks see): reciprocal-square-root seed and two Newton steps
 // with fused multiply-adds, ~1 ulp -- 9 instructions where ot_rcp3(ot_sqrt(x)) takes 17.
 OT_DEV double ot_rsqrt(double x) {

@@ -12,11 +12,17 @@
 #define OT_ST_SQRT 1       // ot_sqrt(|a|)                      against sqrt(|a|)
 #define OT_ST_NORMALIZE 2  // normalize3(a, b, c)               against (a, b, c) / sqrt(a a + b b + c c), component-wise
 #define OT_ST_DIV_SHARED 3 // ot_div_r(a, c, r), ot_div_r(b, c, r) with r = ot_rcp3(c)   against a / c, b / c
+// no exactness case but a measurement: the relative error |1 - a y| of y = the v_rcp_f64 seed, the seed with one and with two
+// Newton steps, and fast_rcp(a) as shipped (one fused multiply-add each, so the error of y is seen to a rounding of itself).
+// Operand class OT_CLS_RECIPROCAL only.  `mismatches` counts the operands on which fast_rcp exceeds OT_FAST_RCP_BOUND;
+// first_bad4 receives the four largest errors in that order.
+#define OT_ST_FAST_RCP 4
 
 #define OT_CLS_WIDE 0      // uniform mantissa, exponent uniform in +-500 (sqrt: -760 .. 1020; normalize3: +-250), random sign
 #define OT_CLS_GEOMETRY 1  // millimetre geometry: magnitude 2^-20 .. 2^14 (log-uniform), random sign
 #define OT_CLS_INDEX 2     // refractive indices: uniform in [1, 2.5]
 #define OT_CLS_COSINE 3    // direction cosines near 0 and near 1: 2^-k m  or  1 - 2^-k m / 2,  k = 0 .. 60, m in [1, 2)
+#define OT_CLS_RECIPROCAL 4  // what refract hands to fast_rcp (M den^2): positive, uniform mantissa, exponent uniform in +-60
 
 OT_DEV double st_make(uint64_t bits, int e_lo, int e_hi, bool sign_rnd) {  // mantissa from bits, exponent in [e_lo, e_hi]
     const uint64_t mant = bits & 0xfffffffffffffull;
@@ -35,6 +41,7 @@ OT_DEV double st_operand(uint64_t bits, int cls, int op) {
             if (op == OT_ST_NORMALIZE) return st_make(bits, -250, 250, true);
             return st_make(bits, -500, 500, true);
         case OT_CLS_GEOMETRY: return st_make(bits, -20, 14, op != OT_ST_SQRT);
+        case OT_CLS_RECIPROCAL: return st_make(bits, -60, 60, false);
         case OT_CLS_INDEX: {
             const double u = (double)(bits >> 11) * 0x1.0p-53;
             return 1.0 + 1.5 * u;
@@ -78,6 +85,36 @@ OT_DEV int st_eval(int op, double a, double b, double c, double* core, double* i
             return 2;
         }
     }
+}
+
+// OT_ST_FAST_RCP: the largest errors of a lane's operands go to bad[0..3] (an atomic maximum on the bits: the errors are not
+// negative, so their order is that of their bit patterns; the buffer starts zeroed)
+OT_DEV void st_max(double* slot, double v) { atomicMax((unsigned long long*)slot, (unsigned long long)__double_as_longlong(v)); }
+
+__global__ __launch_bounds__(256) void selftest_rcp_kernel(int64_t n, uint64_t seed, unsigned long long* __restrict__ out,
+                                                           double* __restrict__ bad) {
+    unsigned long long over = 0;
+    double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        Philox p = philox4x32((uint32_t)i, (uint32_t)(i >> 32), 0x53454c46u, (uint32_t)OT_ST_FAST_RCP, (uint32_t)seed,
+                              (uint32_t)(seed >> 32));
+        const double x = st_operand(((uint64_t)p.c[1] << 32) | p.c[0], OT_CLS_RECIPROCAL, OT_ST_FAST_RCP);
+        const double d0 = fabs(fma(-x, rcp_newton<0>(x), 1.0)), d1 = fabs(fma(-x, rcp_newton<1>(x), 1.0));
+        const double d2 = fabs(fma(-x, rcp_newton<2>(x), 1.0)), d3 = fabs(fma(-x, fast_rcp(x), 1.0));
+        e0 = fmax(e0, d0);
+        e1 = fmax(e1, d1);
+        e2 = fmax(e2, d2);
+        e3 = fmax(e3, d3);
+        if (!(d3 <= OT_FAST_RCP_BOUND)) over++;
+    }
+    st_max(&bad[0], e0);
+    st_max(&bad[1], e1);
+    st_max(&bad[2], e2);
+    st_max(&bad[3], e3);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) over += __shfl_xor(over, o);
+    if ((threadIdx.x & 63) == 0 && over) atomicAdd(&out[0], over);
 }
 
 // out[0] += mismatching operand sets; the first one (lowest index is not guaranteed, any one) goes to bad[0..3] = a, b, c, core

@@ -91,15 +91,6 @@ OT_DEV void compute_polarization(const V3& s, const V3& s_, const RayState& r, f
     }
 }
 
-// 1/x to ~1 ulp: hardware reciprocal seed (v_rcp_f64, ~2^-26... relative) + two Newton steps; only used where the
-// result ends up in a float32 (weights)
-OT_DEV double fast_rcp(double x) {
-    double y = __builtin_amdgcn_rcp(x);
-    y = fma(fma(-x, y, 1.0), y, y);
-    y = fma(fma(-x, y, 1.0), y, y);
-    return y;
-}
-
 // |n x s|^2 below which refraction_polarization drops the plane-of-incidence term of pol', i.e. sin(alpha) = 2^-26: where
 // the form's rounding error (~3 * 2^-53 / sin(alpha)) meets the size of the dropped term (<= sin(alpha)).  From a host sweep
 // of the float64 restatement against exact values (tests/pol_form.py; 2160 rays, sin(alpha) = 2^-30 .. 2^-20, three
@@ -361,90 +352,94 @@ OT_DEV void store_f32(const void* base, uint32_t off, float v) {
     asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dword %1, %2, %0" OT_STORE_HINT : "=&s"(b) : "v"(off), "v"(v), "s"(base) OT_STORE_CLOBBER);
 }
 
-// One section of one ray.  The plane base addresses (array + N * plane) are wave-uniform and stay in SGPRs; the
-// lane contributes the byte offsets of its ray in an f64 plane (`o8` = 8 * index) and in an f32 plane (`o4`),
-// formed once per ray.  The offsets are 32 bits wide: a launch covers at most 2^28 rays (the host entry points
-// split longer bundles and advance the base pointers).
+// One section of one ray.  The plane base addresses `array + N * (section + k * nt)` are wave-uniform; the lane contributes
+// the byte offsets of its ray in an f64 plane (`o8` = 8 * index) and in an f32 plane (`o4`), formed once per ray.  The
+// offsets are 32 bits wide: a launch covers at most 2^28 rays (the host entry points split longer bundles and advance the
+// base pointers).  The bases are 64-bit scalar arithmetic (a plane offset passes 2^32 bytes at 10 M rays; N is the padded
+// plane stride), formed ON DEMAND inside the scalar branch that guards the stores they serve: the step loop carries its
+// section counter and nothing else for them.  A launch that defers planes (ot_scene_set_deferred_planes: the headline
+// trace writes p and w of two sections out of seventeen, neither n nor pol) then pays nothing for the sections it skips.
+// Until round 10 the loop carried eight running bases and N (18 scalar registers, an add pair per base and step, advanced
+// whether the section was stored or not): 46 scalar instructions per wave cheaper than the products when every section was
+// stored (round 3), and dead weight since most launches store next to nothing.  Launches that still store everything are
+// inside their own run-to-run range either way (profiles/r10/store_all.txt).
+// Layout, measured on the bench scene, same box (profiles/r2/store_variants.txt): this form 1.676 ms, per-plane 64-bit
+// VGPR addresses 1.700 ms, a wave-tiled layout ([tile of 64 rays][section][component][lane] inside each array) 1.682 ms --
+// so the reference's planar Fortran layout stays and host views need no re-ordering.  Without the section stores the same
+// kernel ran 1.238 ms at 2.39 GHz; with them the chip held 1.97 GHz: compute and stores do overlap, but together they ran
+// into the package power limit.
+// (on_demand: left to itself the compiler turns the products back into running bases -- it hoists the eight plane bases out
+// of the step loop and advances two running offsets, 24 scalar registers and two add pairs per step whether the section is
+// stored or not.  Behind the empty statement the section is a number it knows nothing about, so the address arithmetic
+// stays inside the branch it is written in.)
+OT_DEV uint32_t on_demand(int sec) {
+    asm("" : "+s"(sec));
+    return (uint32_t)sec;  // (a section or a section count: not negative, and 64 x 32 bits is the cheaper product)
+}
+
+// the polarisation planes of one section alone (ot_rays_fill_pol's kernel stores nothing else)
+OT_DEV void store_pol(const ot_rays& R, uint32_t o4, int sec, float px, float py, float pz) {
+    const uint64_t N = (uint64_t)R.N, first = N * on_demand(sec), plane = N * on_demand(R.nt);  // N * (sec + k * nt)
+    store_f32(R.pol + first, o4, px);
+    store_f32(R.pol + (first + plane), o4, py);
+    store_f32(R.pol + (first + 2 * plane), o4, pz);
+}
 template <bool POL>
 OT_DEV void store_section(const ot_rays& R, uint32_t o8, uint32_t o4, int sec, bool pw, const V3& p, float w, double n,
                           float px, float py, float pz) {
-    // Measured on the bench scene, same box (profiles/r2/store_variants.txt): this form 1.676 ms, per-plane 64-bit
-    // VGPR addresses 1.700 ms, a wave-tiled layout ([tile of 64 rays][section][component][lane] inside each array)
-    // 1.682 ms -- so the reference's planar Fortran layout stays and host views need no re-ordering.  Without the
-    // section stores the same kernel runs 1.238 ms at 2.39 GHz; with them the chip holds 1.97 GHz: compute and stores
-    // do overlap, but together they run into the package power limit.
-    const int64_t N = R.N;
-    const int64_t nt = R.nt;
-    if (pw) {  // (see store_section_next)
-        store_f64(R.p + N * sec, o8, p.x);
-        store_f64(R.p + N * (sec + nt), o8, p.y);
-        store_f64(R.p + N * (sec + 2 * nt), o8, p.z);
-        store_f32(R.w + N * sec, o4, w);
-    }
-    if (R.n) store_f64(R.n + N * sec, o8, n);  // (null: see store_section_next)
-    if (POL && R.pol) {
-        store_f32(R.pol + N * sec, o4, px);
-        store_f32(R.pol + N * (sec + nt), o4, py);
-        store_f32(R.pol + N * (sec + 2 * nt), o4, pz);
-    }
-}
-
-// The same with running plane bases: eight wave-uniform 64-bit pointers that advance by one plane per section (two
-// scalar adds each) instead of eight `array + N * (section + k * nt)` products per section.
-struct PlaneBases {
-    const double *px, *py, *pz, *n;
-    const float *w, *qx, *qy, *qz;
-    int64_t N;
-};
-template <bool POL>
-OT_DEV PlaneBases plane_bases(const ot_rays& R) {
-    const int64_t N = R.N, nt = R.nt;
-    PlaneBases b = {R.p, R.p + N * nt, R.p + N * 2 * nt, R.n, R.w, nullptr, nullptr, nullptr, N};
-    if (POL && R.pol) {  // (null: the polarisation planes are deferred, see store_section_next)
-        b.qx = R.pol;
-        b.qy = R.pol + N * nt;
-        b.qz = R.pol + N * 2 * nt;
-    }
-    return b;
-}
-// the polarisation planes of one section alone (ot_rays_fill_pol's kernel stores nothing else)
-OT_DEV void store_pol_next(PlaneBases& b, uint32_t o4, float px, float py, float pz) {
-    store_f32(b.qx, o4, px);
-    store_f32(b.qy, o4, py);
-    store_f32(b.qz, o4, pz);
-    b.qx += b.N, b.qy += b.N, b.qz += b.N;
-}
-template <bool POL>
-OT_DEV void store_section_next(PlaneBases& b, uint32_t o8, uint32_t o4, bool pw, const V3& p, float w, double n, float px,
-                               float py, float pz) {
     // Position and weight (28 B per section): nothing between a generating trace and an image reads them before section
     // nt - 2, and such a trace can be repeated.  With OT_DEFER_SECTIONS the launcher hands in the range of sections whose
     // planes this launch writes -- [nt - 2, nt) for the trace, [0, nt - 2) for ot_rays_fill_sections -- and `pw` says
-    // whether this section lies in it: section and range are wave-uniform, a scalar branch.  The bases advance either way.
+    // whether this section lies in it: section and range are wave-uniform, a scalar branch.
     if (pw) {
-        store_f64(b.px, o8, p.x);
-        store_f64(b.py, o8, p.y);
-        store_f64(b.pz, o8, p.z);
-        store_f32(b.w, o4, w);
+        const uint64_t N = (uint64_t)R.N, first = N * on_demand(sec), plane = N * on_demand(R.nt);
+        store_f64(R.p + first, o8, p.x);
+        store_f64(R.p + (first + plane), o8, p.y);
+        store_f64(R.p + (first + 2 * plane), o8, p.z);
+        store_f32(R.w + first, o4, w);
     }
     // The index plane is a function of (scene, section, wavelength) alone: with the scene's index store switched off
     // (ot_scene_set_index_store) the launcher hands in a null base, the plane stays unwritten -- 8 of 52 B per section
     // with polarisation -- and ot_rays_fill_index writes it when somebody reads it.  The base is a kernel argument: a
     // scalar branch, the same for every wave of the launch.
-    if (b.n) {
-        store_f64(b.n, o8, n);
-        b.n += b.N;
-    }
-    b.px += b.N, b.py += b.N, b.pz += b.N, b.w += b.N;
+    if (R.n) store_f64(R.n + (uint64_t)R.N * on_demand(sec), o8, n);
     // The polarisation planes (12 of 40 B per section) are read when somebody inspects single rays, and a trace that
     // generates its rays on the device can be repeated: with OT_DEFER_POL (ot_scene_set_deferred_planes) the launcher hands
     // in a null base as well and ot_rays_fill_pol writes the planes later.  The polarisation itself is still computed: the
     // weights depend on it.
-    if (POL && b.qx) store_pol_next(b, o4, px, py, pz);
+    if (POL && R.pol) store_pol(R, o4, sec, px, py, pz);
 }
-#ifndef OT_RUNNING_BASES
-#define OT_RUNNING_BASES 1
-#endif
+
+// The head of a step's hot record by value: kind, form, the step's indices and the ten doubles of the closed-form hit, read
+// at the top of the step as one group of wide scalar loads behind one wait instead of field by field where a block uses
+// them (one round trip to the scalar cache per block).  The rest of the record -- the conic constant, the ring mask, the
+// normal, the ideal lens -- stays where it is and is read where it is used (HotHead: references into the record).
+// The last two doubles are pinned at the top of the step (trace_ray): unpinned they sink into the conic block with a wait
+// of their own.  Measured 1.1257 -> 1.1073 ms on the bench kernel, which has the scalar registers for it since the plane
+// bases are formed on demand (profiles/r10/ab_arms.txt; round 8 had to leave it out for two spilled SGPRs).
+struct HotHeadValues {
+    int32_t kind, form, surf, n_next, filter, hurb, hurb_slot;
+    double px, py, pz, r_eps2, z_max, z_lo, z_hi, k1, inv_rho, two_inv_rho;
+};
+template <class REC>
+struct HotHead : HotHeadValues {
+    decltype((((REC*)nullptr)->k)) k;
+    decltype((((REC*)nullptr)->ri_eps2)) ri_eps2;
+    decltype((((REC*)nullptr)->nrho)) nrho;
+    decltype((((REC*)nullptr)->rho2)) rho2;
+    decltype((((REC*)nullptr)->krho2)) krho2;
+    decltype((((REC*)nullptr)->f)) f;
+    decltype((((REC*)nullptr)->fsign)) fsign;
+};
+template <class REC>
+OT_DEV HotHeadValues hot_head_values(REC& h) {
+    return {h.kind, h.form, h.surf, h.n_next, h.filter, h.hurb, h.hurb_slot, h.px, h.py, h.pz, h.r_eps2, h.z_max, h.z_lo,
+            h.z_hi, h.k1, h.inv_rho, h.two_inv_rho};
+}
+template <class REC>
+OT_DEV HotHead<REC> hot_head(const HotHeadValues& v, REC& h) {
+    return {v, h.k, h.ri_eps2, h.nrho, h.rho2, h.krho2, h.f, h.fsign};
+}
 
 // sub_trace raytracer.py:297-397 for one ray whose section 0 state is in `r`.
 // The element list is flattened on the host into one STEP per tracing surface (lens front, lens back, ideal
@@ -466,7 +461,7 @@ struct TailState {
 };
 // What trace_ray stores: every plane (trace_kernel) / nothing, the TAIL form above / the polarisation planes alone
 // (trace_pol_kernel: the replay behind ot_rays_fill_pol -- the same arithmetic, `R` needs pol, N and nt only).
-// [sec_first, sec_end): with OT_STORE_ALL, the sections whose position and weight planes are written (store_section_next).
+// [sec_first, sec_end): with OT_STORE_ALL, the sections whose position and weight planes are written (store_section).
 #define OT_STORE_ALL 0
 #define OT_STORE_NONE 1
 #define OT_STORE_POL 2
@@ -504,21 +499,16 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
     const auto pool = as_const(sc.pool);
     bool ok = true;
     r.n_cur = (SPEC == 2) ? lrow[(3 * sc.n_steps) * OT_MAX_LINES] : medium_n<TAB>(media[sc.n0], pool, r.wl);
-#if OT_RUNNING_BASES
-    PlaneBases planes = {};
-    if (!TAIL) planes = plane_bases<POL>(R);
-    if (ALL)
-        store_section_next<POL>(planes, o8, o4, sec_first <= 0 && 0 < sec_end, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
-    if (POL_ONLY) store_pol_next(planes, o4, r.polx, r.poly, r.polz);
-#else
-    if (ALL)
-        store_section<POL>(R, o8, o4, 0, sec_first <= 0 && 0 < sec_end, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
-#endif
+    if (ALL) store_section<POL>(R, o8, o4, 0, sec_first <= 0 && 0 < sec_end, r.p, r.w, r.n_cur, r.polx, r.poly, r.polz);
+    if (POL_ONLY) store_pol(R, o4, 0, r.polx, r.poly, r.polz);
 
     for (int i = 0; i < sc.n_steps; i++) {  // i = index of the section the ray starts this step in
         // The step's hot record (ot_scene.hpp::HotStep): what a block of the step reads lies side by side in it, and `form`
         // says whether the record is all the step needs or the surface record is read as well.
-        auto& st = hot[i];
+        // Its head is read here, as one group (HotHeadValues); the empty statement keeps the group's last two doubles in it.
+        auto head = hot_head_values(hot[i]);
+        asm("" : "+s"(head.inv_rho), "+s"(head.two_inv_rho));
+        const auto st = hot_head(head, hot[i]);
         const int form = st.form;
         if (TAIL && i + 1 == sc.n_steps) {  // the last section starts here
             tail->p = r.p;
@@ -614,16 +604,10 @@ OT_DEV bool trace_ray(SC& sc, const ot_rays& R, uint32_t local, uint64_t ray, Ra
         if (i + 1 == sc.n_steps)
 #endif
         {
-#if OT_RUNNING_BASES
-            if (ALL)
-                store_section_next<POL>(planes, o8, o4, sec_first <= i + 1 && i + 1 < sec_end, r.p, r.w, r.n_cur, r.polx,
-                                        r.poly, r.polz);
-            if (POL_ONLY) store_pol_next(planes, o4, r.polx, r.poly, r.polz);
-#else
             if (ALL)
                 store_section<POL>(R, o8, o4, i + 1, sec_first <= i + 1 && i + 1 < sec_end, r.p, r.w, r.n_cur, r.polx,
                                    r.poly, r.polz);
-#endif
+            if (POL_ONLY) store_pol(R, o4, i + 1, r.polx, r.poly, r.polz);
         }
     }
     if (ALL) {

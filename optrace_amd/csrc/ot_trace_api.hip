@@ -229,7 +229,7 @@ static int launch_trace(const ot_scene* sc_c, const ot_sources* src, const Range
         L.part = *rays;
         L.part.p += base; L.part.s += base; L.part.w += base; L.part.n += base; L.part.wl += base;
         if (L.part.pol) L.part.pol += base;
-        // deferred planes: a null base, the kernel skips the plane (ot_trace.hpp::store_section_next).  Rays handed in
+        // deferred planes: a null base, the kernel skips the plane (ot_trace.hpp::store_section).  Rays handed in
         // cannot be repeated and carry their polarisation in section 0 of the plane: ot_trace always stores it.
         if (sc->deferred & OT_DEFER_INDEX) L.part.n = nullptr;
         if ((sc->deferred & OT_DEFER_POL) && src) L.part.pol = nullptr;

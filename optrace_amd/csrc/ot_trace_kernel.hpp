@@ -243,7 +243,7 @@ OT_DEV void flush_counters(TraceLds f, unsigned int* slots) {
 // reduce_counters_kernel, so that no two workgroups hammer the same address (see count_event).
 // The launch covers the rays [ray_base, ray_base + count) of the bundle; R's pointers are advanced to ray_base by
 // the host (R.N stays the plane stride), so lanes address their ray with a 32-bit offset (count <= 2^28).
-// [sec_first, sec_end): the sections whose position and weight planes this launch writes (ot_trace.hpp::store_section_next) --
+// [sec_first, sec_end): the sections whose position and weight planes this launch writes (ot_trace.hpp::store_section) --
 // all of them, the last two (OT_DEFER_SECTIONS) or all but those (ot_rays_fill_sections); kernel arguments, so wave-uniform.
 template <bool POL, bool GEN, int SPEC, int FEAT>
 __global__ __launch_bounds__(256, OT_TRACE_WAVES_STORE(FEAT, SPEC, POL, GEN))
