@@ -831,6 +831,39 @@ int ot_footprint_moments(const ot_rays* rays, int64_t first, int64_t count, cons
 int ot_footprint_maps(const ot_rays* rays, int64_t first, int64_t count, const double* axis, const double* records, int32_t n_px,
                       double* maps, void* stream);
 
+/* ---- chromatic analysis (Raytracer.chromatic_analysis; no counterpart in optrace) --------------------------------
+ * Per band of wavelengths, over the rays [first, first + count) of a storage and its section `section` (0 .. nt - 2): the sums for
+ * the point closest to the band's ray lines, and where the band's rays cross a plane z = const.  key[count] (bytes): the band of
+ * ray first + i, 0 .. n_bands - 1, any other value (255 by convention): in no band.  A ray is used when w[section] > 0 and
+ * d = p[section + 1] - p[section] has a length L > 0, as in the wavefront analysis; positions, weights and wavelengths of
+ * other rays, and of rays of other bands, are not read into a band's arithmetic.  All arithmetic in f64.  Pointers are DEVICE
+ * unless said otherwise; launches are ordered on `stream` and nothing is waited for.  A null argument, a ray range outside the
+ * storage, a section out of range, z or origin not finite: OT_ERR_INVALID; n_bands outside 1 .. OT_CHROM_MAX_BANDS:
+ * OT_ERR_UNSUPPORTED, both before a device is looked for; count = 0 returns OT_OK without a launch and leaves the outputs alone.
+ * ot_chromatic_focus: sums[n_bands * OT_WF_FOCUS_M], per band the sums of ot_wavefront_focus over its used rays, with
+ *   q = p[section] - origin, origin[3] HOST.  Reads key, p and w.
+ * ot_chromatic_plane: records[n_bands * OT_CHROM_M], per band, with t = (z - p_z) / d_z, x = p_x + t d_x, y = p_y + t d_y of
+ *   p = p[section] for its used rays with d_z != 0
+ *    0 sum w          1 rays in the sums   2 sum w x     3 sum w y     4 sum w wl
+ *    5 sum w dx^2     6 sum w dy^2         7 sum w dx dy               (dx, dy) = (x, y) - c, c = (slot 2, slot 3) / slot 0, formed
+ *                                                                      before squaring: a second pass over the planes; NaN when
+ *                                                                      slot 1 is 0
+ *    8 max (dx^2 + dy^2); 0 when slot 1 is 0      9 used rays of the band with d_z == 0, which are in none of the sums
+ *   Reads key, p, w and wl.  Both passes, their last kernels and the finish are queued without a host round trip.  Slots 0, 1, 4
+ *   and 9 do not depend on z.  (Raytracer.chromatic_analysis refers its shifts to the band with used rays whose mean wavelength
+ *   -- the line itself for a band that is one spectral line, slot 4 / slot 0 otherwise, no number when slot 1 is 0 -- lies
+ *   nearest to a reference wavelength.)
+ * workspace >= ot_chromatic_workspace(count, n_bands) doubles (0 for arguments out of range).  All bands go in one launch per
+ * pass; the sums are added in an order fixed by count and n_bands alone: the same call returns the same bits. */
+#define OT_CHROM_M 10
+#define OT_CHROM_MAX_BANDS 32
+#define OT_CHROM_BLOCKS 1024 /* most workgroups per band and 2^28 rays whose partial sums the workspace holds */
+int64_t ot_chromatic_workspace(int64_t count, int32_t n_bands);
+int ot_chromatic_focus(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const uint8_t* key, int32_t n_bands,
+                       const double* origin, double* workspace, double* sums, void* stream);
+int ot_chromatic_plane(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const uint8_t* key, int32_t n_bands,
+                       double z, double* workspace, double* records, void* stream);
+
 /* ---- Huygens point spread function (Raytracer.huygens_psf; no counterpart in optrace) -----------------------------
  * The coherent sum of one spherical wavelet per ray over the points of an image plane, from the rays' places and optical
  * paths on the reference sphere of the wavefront analysis above.  Pointers are DEVICE unless said otherwise; launches are

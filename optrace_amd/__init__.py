@@ -21,6 +21,7 @@ from .spot import SpotAnalysis
 from .wavefront import WavefrontAnalysis
 from .psf import HuygensPSF, HuygensStack
 from .footprint import Footprints
+from .chromatic import ChromaticAnalysis
 from .ray_storage import RayStorage
 from .raytracer import Raytracer
 from .convolve import convolve, convolve_field

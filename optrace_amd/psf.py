@@ -155,6 +155,11 @@ def check_stack_arguments(nt: int, section, focus, radius, n_px, size, dz, bands
     else:
         planes = np.array([_wavefront._finite_number("dz", dz)])
     focus, radius, size, _ = check_arguments(nt, section, focus, radius, n_px, size, 0.0)
+    return focus, radius, size, planes, check_bands(bands)
+
+
+def check_bands(bands):
+    """The checks of `bands`, for `huygens_stack` and `chromatic_analysis`.  -> "lines", an int or a float64 array of edges."""
     if isinstance(bands, str):
         if bands != "lines":
             raise ValueError(f"Property 'bands' needs to be 'lines', a number of bands or a sequence of edges, but is '{bands}'.")
@@ -171,7 +176,7 @@ def check_stack_arguments(nt: int, section, focus, radius, n_px, size, dz, bands
         check_type("bands", bands, int)
         check_not_below("bands", bands, 1)
         check_not_above("bands", bands, _capi.PSF_MAX_BANDS)
-    return focus, radius, size, planes, bands
+    return bands
 
 
 class DiffractionMTF(BaseClass):

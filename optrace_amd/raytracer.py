@@ -39,6 +39,8 @@ from . import psf as _psf
 from .psf import HuygensPSF, HuygensStack
 from . import footprint as _footprint
 from .footprint import Footprints
+from . import chromatic as _chromatic
+from .chromatic import ChromaticAnalysis
 from .geometry.ray_source import RaySource
 from .scene import CompiledScene, SectionTable, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
@@ -875,6 +877,21 @@ class Raytracer(Group):
         axis, radii = table.axes_and_radii(source_index)
         labels = table.labels("sources" if source_index is None else who)
         return _footprint.analyse(self.rays, Ns, Ne - Ns, axis, n_px, labels, radii, long_desc=f"Footprints of {who}")
+
+    def chromatic_analysis(self, source_index: int = 0, section: int = None, bands="lines", z: float = None,
+                           reference: float = None) -> ChromaticAnalysis:
+        """Chromatic focal shift and lateral colour of one source's rays (None: all rays), no counterpart in optrace: per band of
+        wavelengths the point closest to the band's ray lines, and centroid, RMS size and largest radius of where the band
+        crosses a common plane, reduced on the GPU from the position, weight and wavelength planes of one section (chromatic.py).
+        section: as for `wavefront_analysis`; bands: as for `huygens_stack`, "lines", a number of equal bands or ascending edges
+        in nm, 32 bands at the most; z: absolute z of the plane, default the focus z of the reference band; reference: a
+        wavelength in nm, the band with rays whose mean wavelength lies nearest to it is the one the shifts refer to, default
+        the power-weighted mean wavelength of the used rays."""
+        table = SectionTable(self)
+        bands, z, reference = _chromatic.check_arguments(table.nt, section, bands, z, reference)
+        Ns, Ne, k, origin, label = self._section_bundle(table, source_index, section, "the chromatic figures hold")
+        return _chromatic.analyse(self.rays, Ns, Ne - Ns, k, origin, bands, z, reference,
+                                  long_desc=f"Chromatic analysis of {label} behind section {k}")
 
     def _section_bundle(self, table: SectionTable, source_index, section, holds: str):
         """What the analyses of a stored section share, after their own argument checks against `table.nt`: the device, current

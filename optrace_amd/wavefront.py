@@ -153,6 +153,19 @@ def _empty(section: int, focus, radius, n_zernike: int, n_grid: int, n_missed: i
                              np.zeros((n_grid, n_grid)), **kwargs)
 
 
+def closest_point(sums, origin):
+    """The point closest to all ray lines from the sums of `ot_wavefront_focus` (float64 host arithmetic), three NaN where the
+    system is singular or its solution not finite (a collimated bundle): the singularity test of the wavefront analysis, which the
+    chromatic analysis shares."""
+    f = np.asarray(sums, dtype=np.float64)
+    A = np.array([[f[8], f[9], f[10]], [f[9], f[11], f[12]], [f[10], f[12], f[13]]])
+    try:
+        focus = origin + np.linalg.solve(A, f[14:17])
+    except np.linalg.LinAlgError:
+        focus = np.full(3, np.nan)
+    return focus if np.all(np.isfinite(focus)) else np.full(3, np.nan)
+
+
 def reference_sphere(sums, origin, focus, radius):
     """Centre and signed radius of the default reference sphere from the sums of `ot_wavefront_focus` (float64 host arithmetic):
     the centre is the point closest to all ray lines, the radius its distance from the mean start of the section, positive
@@ -160,11 +173,7 @@ def reference_sphere(sums, origin, focus, radius):
     f = np.asarray(sums, dtype=np.float64)
     W = f[0]
     if focus is None:
-        A = np.array([[f[8], f[9], f[10]], [f[9], f[11], f[12]], [f[10], f[12], f[13]]])
-        try:
-            focus = origin + np.linalg.solve(A, f[14:17])
-        except np.linalg.LinAlgError:
-            focus = np.full(3, np.nan)
+        focus = closest_point(f, origin)
         if not np.all(np.isfinite(focus)):
             raise RuntimeError("The rays of the section have no common closest point (a collimated bundle?): "
                                "pass `focus` and `radius`.")
