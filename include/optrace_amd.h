@@ -864,6 +864,47 @@ int ot_chromatic_focus(const ot_rays* rays, int64_t first, int64_t count, int32_
 int ot_chromatic_plane(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const uint8_t* key, int32_t n_bands,
                        double z, double* workspace, double* records, void* stream);
 
+/* ---- ray fans (Raytracer.ray_fans; no counterpart in optrace) ----------------------------------------------------
+ * Per band of wavelengths the transverse ray aberration and the optical path difference along two cuts of the pupil, from the
+ * dense planes u, v, opl, w_out that ot_wavefront_paths left for the rays [first, first + count) and the moments record of
+ * ot_wavefront_moments.  key[count] (bytes): the band of entry i, 0 .. n_bands - 1, any other value (255 by convention): in no
+ * band.  An entry counts when w > 0; the other planes of entries that do not count, and of other bands, are not read into a
+ * band's arithmetic.  All arithmetic in f64.  Pointers are DEVICE unless said otherwise; launches are ordered on `stream` and
+ * nothing is waited for.  A null argument, count < 0, a ray range outside the storage, a section out of range, a focus that is
+ * not finite, slab outside (0, 1], a pupil radius that is neither NaN nor above zero: OT_ERR_INVALID; n_bands outside
+ * 1 .. OT_CHROM_MAX_BANDS, n_bins outside 1 .. OT_FAN_MAX_BINS: OT_ERR_UNSUPPORTED, both before a device is looked for;
+ * count = 0 returns OT_OK without a launch and leaves the outputs alone.
+ * ot_fans_transverse: for the entries with w > 0 (w[count], f32: the w_out of ot_wavefront_paths), with p = p[section],
+ *   d = p[section + 1] - p and t = (focus_z - p_z) / d_z: ex = p_x + t d_x - focus_x, ey = p_y + t d_y - focus_y, where the ray
+ *   crosses the plane z = focus z, against the focus (focus[3] HOST).  An entry with d_z == 0 is counted in *n_parallel and
+ *   its w is set to 0, here, in place; it and the entries with w = 0 get NaN in ex and ey.  Reads p.
+ * ot_fans_bands: records[n_bands * OT_FAN_M], per band over its entries with w > 0
+ *    0 sum w          1 entries        2 sum w opl      3 sum w ex       4 sum w ey       5 sum w wl
+ *    6 min opl        7 max opl                                                           0 when slot 1 is 0
+ *    8 sum w opd^2    9 sum w dex^2   10 sum w dey^2   11 sum w dex dey                   opd = opl - slot 2 / slot 0, (dex, dey) =
+ *                                                       (ex, ey) - (slot 3, slot 4) / slot 0, formed before squaring: a second
+ *                                                       pass over the planes; slots 9 .. 11 NaN when slot 1 is 0, slot 8 is 0
+ *   12 max (dex^2 + dey^2); 0 when slot 1 is 0
+ *   workspace >= ot_fans_workspace(count, n_bands) doubles (0 for arguments out of range).  All bands go in one launch per
+ *   pass; the sums are added in an order fixed by count and n_bands alone: the same call returns the same bits.
+ * ot_fans_bins: out[n_bands][2][n_bins][OT_FAN_BIN_M] (accumulated into: zero it first).  (x, y) = ((u, v) - mean) / pupil
+ *   radius as for ot_wavefront_map (pupil_radius NaN: moments[10]; otherwise entries with x^2 + y^2 > 1 are left out).  Fan 0,
+ *   the tangential one, takes an entry when |x| <= slab and bins c = y; fan 1, the sagittal one, takes it when |y| <= slab and
+ *   bins c = x; bin = min(floor((c + 1) / 2 * n_bins), n_bins - 1), not below 0.  Per bin, of the entries of the band:
+ *    0 sum w    1 entries    2 sum w c    3 sum w ex    4 sum w ey    5 sum w opd, opd = opl - slot 2 / slot 0 of the band's
+ *   record (as ot_fans_bands left it).  Slot 1 is exact; the other sums depend on the order of arrival (f64 atomics). */
+#define OT_FAN_M 13
+#define OT_FAN_BIN_M 6
+#define OT_FAN_MAX_BINS 256
+int64_t ot_fans_workspace(int64_t count, int32_t n_bands);
+int ot_fans_transverse(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const double* focus, float* w, double* ex,
+                       double* ey, int64_t* n_parallel, void* stream);
+int ot_fans_bands(int64_t count, const double* opl, const double* ex, const double* ey, const float* w, const float* wl,
+                  const uint8_t* key, int32_t n_bands, double* workspace, double* records, void* stream);
+int ot_fans_bins(int64_t count, const double* u, const double* v, const double* opl, const double* ex, const double* ey, const float* w,
+                 const uint8_t* key, const double* moments, double pupil_radius, const double* records, int32_t n_bands, int32_t n_bins,
+                 double slab, double* out, void* stream);
+
 /* ---- Huygens point spread function (Raytracer.huygens_psf; no counterpart in optrace) -----------------------------
  * The coherent sum of one spherical wavelet per ray over the points of an image plane, from the rays' places and optical
  * paths on the reference sphere of the wavefront analysis above.  Pointers are DEVICE unless said otherwise; launches are

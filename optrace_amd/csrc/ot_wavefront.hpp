@@ -134,23 +134,7 @@ __global__ __launch_bounds__(OT_RED_THREADS) void wf_central_kernel(int64_t n, c
 // The pupil radius the later passes divide by when the caller gives none, stored so that the host reports this very number
 __global__ void wf_pupil_radius_kernel(double* __restrict__ mom) { mom[WF_PUPIL_R] = ot_sqrt(mom[WF_R2MAX]); }
 
-// Unit-disc coordinates of an entry.  pupil_radius NaN: the largest distance from the pupil centre (moments), every entry
-// inside; otherwise the caller's, and entries beyond it are left out.  All entries in one place: the centre of the disc.
-struct WfPupil {
-    double cu, cv, radius;
-    bool given;
-};
-OT_DEV WfPupil wf_pupil(const double* __restrict__ mom, double pupil_radius) {
-    const WfMeans c = wf_means(mom);
-    const bool given = pupil_radius == pupil_radius;
-    return {c.u, c.v, given ? pupil_radius : mom[WF_PUPIL_R], given};
-}
-OT_DEV bool wf_unit_disc(const WfPupil& P, double u, double v, double* x, double* y) {
-    const bool spread = P.radius > 0.0;
-    *x = spread ? (u - P.cu) / P.radius : 0.0;
-    *y = spread ? (v - P.cv) / P.radius : 0.0;
-    return !(P.given && *x * *x + *y * *y > 1.0);
-}
+// (the unit-disc coordinates of an entry, wf_pupil and wf_unit_disc: ot_wavefront_ray.hpp)
 
 // map[2][n_grid][n_grid] += w | w opd, row = cell of y, column = cell of x, cell = min(floor((x + 1) / 2 n_grid), n_grid - 1).
 // LDS-privatised when the sums fit (lds_cells = 2 n_grid^2), otherwise global atomics.

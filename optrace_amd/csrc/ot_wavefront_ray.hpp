@@ -1,6 +1,6 @@
-// Per-ray device functions of the wavefront analysis that more than one translation unit needs (ot_wavefront.hpp: focus and
-// paths; ot_psf.hpp: the ray records of the Huygens sum): the rays of a section, their sphere step, the slots of the moments
-// record.  No kernels here.
+// Per-ray device functions of the wavefront analysis that more than one translation unit needs (ot_wavefront.hpp: focus,
+// paths, map and fit; ot_psf.hpp: the ray records of the Huygens sum; ot_fans.hpp: the pupil cuts): the rays of a section, their
+// sphere step, the slots of the moments record, the unit-disc coordinates of an entry.  No kernels here.
 #pragma once
 #include "ot_device.hpp"
 
@@ -73,3 +73,21 @@ struct WfMeans {
     double opl, u, v;
 };
 OT_DEV WfMeans wf_means(const double* __restrict__ mom) { return {mom[WF_WOPL] / mom[WF_W], mom[WF_WU] / mom[WF_W], mom[WF_WV] / mom[WF_W]}; }
+
+// Unit-disc coordinates of an entry.  pupil_radius NaN: the largest distance from the pupil centre (moments), every entry
+// inside; otherwise the caller's, and entries beyond it are left out.  All entries in one place: the centre of the disc.
+struct WfPupil {
+    double cu, cv, radius;
+    bool given;
+};
+OT_DEV WfPupil wf_pupil(const double* __restrict__ mom, double pupil_radius) {
+    const WfMeans c = wf_means(mom);
+    const bool given = pupil_radius == pupil_radius;
+    return {c.u, c.v, given ? pupil_radius : mom[WF_PUPIL_R], given};
+}
+OT_DEV bool wf_unit_disc(const WfPupil& P, double u, double v, double* x, double* y) {
+    const bool spread = P.radius > 0.0;
+    *x = spread ? (u - P.cu) / P.radius : 0.0;
+    *y = spread ? (v - P.cv) / P.radius : 0.0;
+    return !(P.given && *x * *x + *y * *y > 1.0);
+}

@@ -41,6 +41,8 @@ from . import footprint as _footprint
 from .footprint import Footprints
 from . import chromatic as _chromatic
 from .chromatic import ChromaticAnalysis
+from . import fans as _fans
+from .fans import RayFans
 from .geometry.ray_source import RaySource
 from .scene import CompiledScene, SectionTable, tracing_elements
 from ._device import require_device, stream_ptr, ptr, alloc_retry, mailbox
@@ -892,6 +894,21 @@ class Raytracer(Group):
         Ns, Ne, k, origin, label = self._section_bundle(table, source_index, section, "the chromatic figures hold")
         return _chromatic.analyse(self.rays, Ns, Ne - Ns, k, origin, bands, z, reference,
                                   long_desc=f"Chromatic analysis of {label} behind section {k}")
+
+    def ray_fans(self, source_index: int = 0, section: int = None, bands="lines", focus=None, radius: float = None,
+                 n_bins: int = 32, slab: float = 0.1, pupil_radius: float = None) -> RayFans:
+        """Ray aberration fans of one source's rays (None: all rays), no counterpart in optrace: per band of wavelengths the
+        transverse ray aberration in the plane of the focus and the optical path difference against the pupil coordinate, along
+        the tangential and the sagittal cut of the pupil, and the band's own wavefront and spot figures, reduced on the GPU
+        (fans.py).  section, focus, radius, pupil_radius: as for `wavefront_analysis`, one reference sphere and one pupil for all
+        bands; bands: as for `chromatic_analysis`; n_bins: bins over the pupil coordinate -1 .. 1, 1 to 256; slab: half width of
+        a cut in units of the pupil radius, above 0 and at most 1."""
+        table = SectionTable(self)
+        bands, focus, radius, slab, pupil_radius = _fans.check_arguments(table.nt, section, bands, focus, radius, n_bins, slab,
+                                                                         pupil_radius)
+        Ns, Ne, k, origin, label = self._section_bundle(table, source_index, section, "the ray fans hold")
+        return _fans.analyse(self.rays, Ns, Ne - Ns, k, origin, bands, focus, radius, n_bins, slab, pupil_radius,
+                             long_desc=f"Ray fans of {label} behind section {k}")
 
     def _section_bundle(self, table: SectionTable, source_index, section, holds: str):
         """What the analyses of a stored section share, after their own argument checks against `table.nt`: the device, current
