@@ -864,6 +864,36 @@ int ot_chromatic_focus(const ot_rays* rays, int64_t first, int64_t count, int32_
 int ot_chromatic_plane(const ot_rays* rays, int64_t first, int64_t count, int32_t section, const uint8_t* key, int32_t n_bands,
                        double z, double* workspace, double* records, void* stream);
 
+/* ---- field analysis (Raytracer.field_analysis; no counterpart in optrace) ----------------------------------------
+ * Per field point and band of wavelengths the first and second moments of the ray lines of section `section` (0 .. nt - 2).
+ * fields[n_fields][2] HOST: (first, count) of every field's rays in the storage; the ranges need not touch.  key (bytes):
+ * key[r - key_first] is the band of ray r, 0 .. n_bands - 1, any other value (255 by convention): in no band; it covers
+ * every field's range.  A ray is used when w[section] > 0 and d = p[section + 1] - p[section] has a length above 0; positions,
+ * weights and wavelengths of other rays and of rays in no band are not read into arithmetic.  With q = p[section] - origin
+ * (origin[3] HOST), m = (d_x, d_y) / d_z and a = (q_x, q_y) - q_z m -- the ray crosses a plane z at
+ * origin_xy + a + (z - origin_z) m --, records[n_fields][n_bands][OT_FIELD_M] holds over the cell's used rays with d_z != 0
+ *    0 sum w        1 rays in the sums   2 sum w a_x   3 sum w a_y   4 sum w m_x   5 sum w m_y   6 sum w wl
+ *    7 used rays of the cell with d_z == 0, which are in none of the sums
+ *    8 sum w da_x^2      9 sum w da_x da_y   10 sum w da_y^2
+ *   11 sum w da_x dm_x  12 sum w da_x dm_y   13 sum w da_y dm_x   14 sum w da_y dm_y
+ *   15 sum w dm_x^2     16 sum w dm_x dm_y   17 sum w dm_y^2
+ *   da = a - (slot 2, slot 3) / slot 0, dm = m - (slot 4, slot 5) / slot 0, formed before multiplying: a second pass over the
+ *   planes; slots 8 .. 17 are NaN when slot 1 is 0.  All arithmetic in f64.
+ * Both passes request every ray's data once, whatever n_fields and n_bands are: the key byte of every ray of a field, and of a
+ * ray with a band w, p[section], p[section + 1] and, in the first pass, wl.  Both passes, their last kernels and the finish are
+ * queued on `stream` without a host round trip, and nothing is waited for.  The sums of a field are added in an order fixed by
+ * its count and n_bands alone: the same call returns the same bits, and a field's records do not depend on the other fields.
+ * A null argument, a ray range outside the storage, a field with rays that starts before key_first, a section out of range,
+ * origin not finite: OT_ERR_INVALID; n_fields outside 1 .. OT_FIELD_MAX_FIELDS or n_bands outside 1 .. OT_CHROM_MAX_BANDS:
+ * OT_ERR_UNSUPPORTED, both before a device is looked for; no ray in any field returns OT_OK without a launch and leaves the
+ * outputs alone.  workspace >= ot_field_workspace(fields, n_fields, n_bands) doubles (0 for arguments out of range). */
+#define OT_FIELD_M 18
+#define OT_FIELD_MAX_FIELDS 64
+#define OT_FIELD_BLOCKS 1024 /* most workgroups per field and 2^28 rays whose partial sums the workspace holds */
+int64_t ot_field_workspace(const int64_t* fields, int32_t n_fields, int32_t n_bands);
+int ot_field_sums(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key, int64_t key_first,
+                  int32_t n_bands, const double* origin, double* workspace, double* records, void* stream);
+
 /* ---- ray fans (Raytracer.ray_fans; no counterpart in optrace) ----------------------------------------------------
  * Per band of wavelengths the transverse ray aberration and the optical path difference along two cuts of the pupil, from the
  * dense planes u, v, opl, w_out that ot_wavefront_paths left for the rays [first, first + count) and the moments record of

@@ -22,6 +22,7 @@ from .wavefront import WavefrontAnalysis
 from .psf import HuygensPSF, HuygensStack
 from .footprint import Footprints
 from .chromatic import ChromaticAnalysis
+from .field import FieldAnalysis
 from .fans import RayFans
 from .ray_storage import RayStorage
 from .raytracer import Raytracer

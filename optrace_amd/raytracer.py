@@ -41,6 +41,8 @@ from . import footprint as _footprint
 from .footprint import Footprints
 from . import chromatic as _chromatic
 from .chromatic import ChromaticAnalysis
+from . import field as _field
+from .field import FieldAnalysis
 from . import fans as _fans
 from .fans import RayFans
 from .geometry.ray_source import RaySource
@@ -894,6 +896,49 @@ class Raytracer(Group):
         Ns, Ne, k, origin, label = self._section_bundle(table, source_index, section, "the chromatic figures hold")
         return _chromatic.analyse(self.rays, Ns, Ne - Ns, k, origin, bands, z, reference,
                                   long_desc=f"Chromatic analysis of {label} behind section {k}")
+
+    def field_analysis(self, sources=None, section: int = None, bands="lines", z: float = None, reference: float = None,
+                       reference_field: int = 0, paraxial: str = "tma") -> FieldAnalysis:
+        """How the image changes across the field, no counterpart in optrace: every chosen ray source is a field point, and per
+        field point and band of wavelengths the tangential, sagittal and best-RMS focus (astigmatism, field curvature), the
+        centroid on a common plane against its paraxial image (distortion), the spot size and the power (relative illumination)
+        are reduced on the GPU in one call, from the position, weight and wavelength planes of one section (field.py).
+        sources: None for every ray source or 1 to 64 distinct source indices, the field points in that order; section: as for
+        `wavefront_analysis`; bands, reference: as for `chromatic_analysis`, the bands assigned over the used rays of all chosen
+        fields together; reference_field: index into `sources` of the field the curvatures and the illumination refer to; z:
+        absolute z of the common plane, default the best-RMS focus of the reference field in the reference band; paraxial: "tma"
+        for paraxial image points from the transfer matrix analysis of the geometry (NaN where it has none), None for none."""
+        table = SectionTable(self)
+        sources, bands, z, reference = _field.check_arguments(table.nt, len(self.ray_sources), sources, section, bands, z, reference,
+                                                              reference_field, paraxial)
+        require_device()  # (said before anything about the rays: without a device there are none)
+        ranges = []
+        for s in sources:
+            Ns, Ne = self._stored_range(s)
+            ranges.append((Ns, Ne - Ns))
+        k = table.nt - 2 if section is None else section
+        axis = np.array(self.lenses[0].pos[:2], dtype=np.float64) if self.lenses else np.zeros(2)
+        positions, tangents, field, power = [], [], [], []
+        for s in sources:
+            rs = self.ray_sources[s]
+            pos = np.array(rs.pos, dtype=np.float64) - [axis[0], axis[1], 0.0]
+            sv = np.array(rs.s, dtype=np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                tan = sv[:2] / sv[2] if rs.orientation == "Constant" else np.full(2, np.nan)
+            positions.append(pos)
+            tangents.append(tan)
+            field.append(pos[:2] if np.any(pos[:2] != 0) else tan)
+            power.append(float(rs.power))
+
+        def matrix_at(wl, z_g, z_b):
+            try:
+                return self.tma(wl).matrix_at(z_g, z_b)
+            except Exception:  # (no lenses, no symmetry, a plane inside a lens: no paraxial image, which the result says with NaN)
+                return None
+
+        return _field.analyse(self.rays, ranges, k, table.origin(k, None), bands, z, reference, reference_field, sources, field,
+                              power, positions, tangents, matrix_at if paraxial == "tma" else None, axis,
+                              long_desc=f"Field analysis of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
 
     def ray_fans(self, source_index: int = 0, section: int = None, bands="lines", focus=None, radius: float = None,
                  n_bins: int = 32, slab: float = 0.1, pupil_radius: float = None) -> RayFans:
