@@ -894,6 +894,41 @@ int64_t ot_field_workspace(const int64_t* fields, int32_t n_fields, int32_t n_ba
 int ot_field_sums(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key, int64_t key_first,
                   int32_t n_bands, const double* origin, double* workspace, double* records, void* stream);
 
+/* ---- MTF analysis (Raytracer.mtf_analysis; no counterpart in optrace) ---------------------------------------------
+ * Per field point, band of wavelengths, plane and spatial frequency the geometric OTF sums of the ray lines of section `section`,
+ * along the tangential direction of the field and across it.  rays, fields, section, key, key_first, n_bands, origin: those of the
+ * ot_field_sums call that wrote records[n_fields][n_bands][OT_FIELD_M] (DEVICE); the used rays, their bands and their lines
+ * origin_xy + a + (z - origin_z) m are the ones of that call, formed by the same operations, and rays with d_z == 0 enter no sum.
+ * About the means of the cell, da = a - (slot 2, slot 3) / slot 0, dm = m - (slot 4, slot 5) / slot 0 -- the quotients the second
+ * pass of ot_field_sums forms --, with t = (t[f][0], t[f][1]) of the ray's field (t[n_fields][2] HOST) and s = (-t_y, t_x):
+ *    al_t = t_x da_x + t_y da_y   mu_t = t_x dm_x + t_y dm_y   al_s = s_x da_x + s_y da_y   mu_s = s_x dm_x + s_y dm_y
+ * and per plane j (zeta[n_planes] HOST: the plane's z minus origin_z) and frequency q (freq[n_freq] DEVICE, cycles per length):
+ *    e = al + zeta_j mu,  tau = freq_q e,  tau -= rint(tau),  (sn, cs) = sin, cos (2 pi tau)
+ *    sums[f][b][j][q] = (sum w cs_t, -sum w sn_t, sum w cs_s, -sum w sn_s)
+ * over the rays in the record's sums: divided by slot 0 the OTF of the cell on the plane about its centroid there.  All arithmetic
+ * in f64 without fused multiply-adds outside the sine and cosine.  A cell without a ray in the record's sums (slot 1 is 0) gets
+ * zeros.  The launches are queued on `stream` without a host round trip, and nothing is waited for.  The sums of a field are added
+ * in an order fixed by its count and (n_bands, n_planes, n_freq) alone: the same call returns the same bits, and a field's sums do
+ * not depend on the other fields.  No atomics.
+ * A null argument, a ray range outside the storage, a field with rays that starts before key_first, a section out of range,
+ * origin, t or zeta not finite: OT_ERR_INVALID; n_fields outside 1 .. OT_FIELD_MAX_FIELDS, n_bands outside 1 ..
+ * OT_CHROM_MAX_BANDS, n_planes outside 1 .. OT_MTF_MAX_PLANES or n_freq outside 1 .. OT_MTF_MAX_FREQ: OT_ERR_UNSUPPORTED, both
+ * before a device is looked for; no ray in any field returns OT_OK without a launch and leaves the outputs alone.
+ * workspace >= ot_mtf_workspace(fields, n_fields, n_bands, n_planes, n_freq) doubles (0 for arguments out of range): per field a
+ * list of partials as long as the longest field's; a workgroup takes a group of KB = min(n_bands, 4) bands side by side and a tile
+ * of TILE = 8 / KB (plane, frequency) pairs, 3 for KB = 3, and writes a partial of KB * 4 * TILE doubles; a field has a workgroup
+ * per 256 rays, at most max(OT_MTF_MIN_BLOCKS, OT_MTF_BLOCKS / (groups * tiles)) per 2^28 rays.  A ray whose phase is no number
+ * (|freq e| beyond the range of a double) turns the sums of that plane and frequency into no numbers for its own band and for
+ * the other bands of its group in its field. */
+#define OT_MTF_MAX_FREQ 64
+#define OT_MTF_MAX_PLANES 65
+#define OT_MTF_BLOCKS 1024   /* workgroups per field and 2^28 rays over all groups of bands and tiles, about */
+#define OT_MTF_MIN_BLOCKS 16 /* ... and the fewest the largest fields are walked by */
+int64_t ot_mtf_workspace(const int64_t* fields, int32_t n_fields, int32_t n_bands, int32_t n_planes, int32_t n_freq);
+int ot_mtf_sums(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key, int64_t key_first,
+                int32_t n_bands, const double* origin, const double* records, const double* t, const double* zeta, int32_t n_planes,
+                const double* freq, int32_t n_freq, double* workspace, double* sums, void* stream);
+
 /* ---- ray fans (Raytracer.ray_fans; no counterpart in optrace) ----------------------------------------------------
  * Per band of wavelengths the transverse ray aberration and the optical path difference along two cuts of the pupil, from the
  * dense planes u, v, opl, w_out that ot_wavefront_paths left for the rays [first, first + count) and the moments record of

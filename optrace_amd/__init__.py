@@ -23,6 +23,7 @@ from .psf import HuygensPSF, HuygensStack
 from .footprint import Footprints
 from .chromatic import ChromaticAnalysis
 from .field import FieldAnalysis
+from .mtf import MTFAnalysis
 from .fans import RayFans
 from .ray_storage import RayStorage
 from .raytracer import Raytracer

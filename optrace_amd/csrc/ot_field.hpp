@@ -12,13 +12,13 @@
 #pragma once
 #include "ot_block_reduce.hpp"
 #include "ot_device.hpp"
+#include "ot_field_ray.hpp"
 
 // slots of the record (include/optrace_amd.h, ot_field_sums): pass 1 carries the first FD_M1 of them, pass 2 the rest
 enum { FD_W = 0, FD_COUNT, FD_WAX, FD_WAY, FD_WMX, FD_WMY, FD_WWL, FD_PARALLEL, FD_M1,
        FD_AXAX = FD_M1, FD_AXAY, FD_AYAY, FD_AXMX, FD_AXMY, FD_AYMX, FD_AYMY, FD_MXMX, FD_MXMY, FD_MYMY, FD_M };
 static_assert(FD_M == OT_FIELD_M && FD_M1 == 8, "the record of the header");
 #define FD_M2 (FD_M - FD_M1)
-#define FD_NO_BAND 255u
 
 // One launch takes up to FD_PIECES pieces; a piece is a field's range, or 2^28 rays of it: 32-bit offsets from `base`.
 #define FD_PIECES 64
@@ -32,39 +32,6 @@ struct FdPiece {
 struct FdBatch {
     FdPiece piece[FD_PIECES];
 };
-
-// The planes of section k from the first ray of a piece on.  Workgroup-uniform.
-struct FdSection {
-    const uint8_t* key;
-    const float *w, *wl;
-    const double *x0, *y0, *z0, *x1, *y1, *z1;
-};
-OT_DEV FdSection fd_section(const double* __restrict__ p, const float* __restrict__ w, const float* __restrict__ wl,
-                            const uint8_t* __restrict__ key, int64_t N, int nt, int k) {
-    return {key, w + N * k, wl, p + N * k, p + N * (k + nt), p + N * (k + 2 * (int64_t)nt), p + N * (k + 1), p + N * (k + 1 + nt),
-            p + N * (k + 1 + 2 * (int64_t)nt)};
-}
-
-// Ray r, whose key is a band (definition, steps 1 and 2): used?  Then its weight, d_z, and, where d_z != 0, the line (a, m).
-struct FdRay {
-    double w, dz, ax, ay, mx, my;
-};
-OT_DEV bool fd_ray(const FdSection& S, uint32_t r, double ox, double oy, double oz, FdRay& q) {
-    const float wi = S.w[r];
-    if (!(wi > 0.f)) return false;
-    const double px = S.x0[r], py = S.y0[r], pz = S.z0[r];
-    const double dx = S.x1[r] - px, dy = S.y1[r] - py, dz = S.z1[r] - pz;
-    if (!(dx * dx + dy * dy + dz * dz > 0.0)) return false;  // (the square of a length above 0, and no NaN)
-    q.w = (double)wi;
-    q.dz = dz;
-    if (dz == 0.0) return true;
-    const double qx = px - ox, qy = py - oy, qz = pz - oz;
-    q.mx = dx / dz;
-    q.my = dy / dz;
-    q.ax = qx - qz * q.mx;
-    q.ay = qy - qz * q.my;
-    return true;
-}
 
 // The band sums of a wave.  The lanes change roles: lane (t, j) = (lane / J, lane % J), J = 64 / M, owns slot t of the bands
 // j, j + J, ..., NC of them, in registers for the whole walk.  Per step every lane puts the M values of its ray into the wave's

@@ -195,22 +195,25 @@ def paraxial_images(matrix_at, wavelengths, positions, tangents, z: float):
     return out
 
 
-def analyse(rays, ranges, section: int, origin, bands, z, reference, reference_field: int, sources, field, power, positions,
-            tangents, matrix_at, axis=(0.0, 0.0), **kwargs) -> FieldAnalysis:
-    """Figures of the fields `ranges` [(first, count), ...] of the storage `rays` in section `section`; origin: the point the device
-    refers the lines to; bands, z, reference as `check_arguments` returned them; sources, field, power, positions (relative to the
-    optical axis `axis`), tangents: per field, what `FieldAnalysis` and `paraxial_images` take; matrix_at: see `paraxial_images`.  Reads the
-    p, w and wl planes only.  Reads of the device: for "lines" the table of lines, 33 doubles, before the launches; one for the
-    records (with the edges for a number of bands).  The default `reference` is the power-weighted mean wavelength of the rays in
-    the sums."""
+class _Front:
+    """What `band_records` hands on: the launch of `ot_field_sums` and what the host made of it."""
+    __slots__ = ("R", "flat", "F", "lo", "key8", "K", "d_rec", "keep", "rec", "origin", "edges", "reference", "reference_band")
+
+
+def band_records(rays, ranges, section: int, origin, bands, reference):
+    """The front half of the analyses per field and band (`analyse` here, `mtf.analyse`): the used rays of the chosen fields as the
+    kernels test them, their band keys, the `ot_field_sums` launch, `psf.settle_bands` and the reference band.  -> None when no ray
+    is left in any band, else a `_Front`: R, flat, F, lo, key8, K, d_rec -- the arguments of the launch and the device tensor of
+    its full records (F, K, 18) --, keep: the slice of the K bands that are left, rec = records[:, keep] on the host, origin as an
+    array, edges, reference and reference_band.  Reads of the device: for "lines" the table of lines, 33 doubles, before the
+    launches; one for the records (with the edges for a number of bands)."""
     import torch
     from ._device import require_device, ptr, stream_ptr
     lib = _capi.load_library()
     dev = require_device()
-    fixed = dict(origin=origin, reference_field=reference_field, sources=sources, field=field, power=power, axis=axis)
     some = [(a, n) for a, n in ranges if n > 0]
     if not some:
-        return _empty(section, bands, z, **fixed, **kwargs)
+        return None
     F = len(ranges)
     lo, hi = min(a for a, _ in some), max(a + n for a, n in some)
     span = hi - lo
@@ -241,10 +244,10 @@ def analyse(rays, ranges, section: int, origin, bands, z, reference, reference_f
     M = _capi.FIELD_M
     flat = (C.c_int64 * (2 * F))(*[int(v) for pair in ranges for v in pair])
     ws = torch.empty(max(1, lib.ot_field_workspace(flat, F, K)), dtype=torch.float64, device=dev)
-    rec = torch.zeros(F * K * M, dtype=torch.float64, device=dev)
+    d_rec = torch.zeros(F * K * M, dtype=torch.float64, device=dev)
     origin = np.array(origin, dtype=np.float64)
-    _capi.check(lib.ot_field_sums(C.byref(R), flat, F, k, ptr(key8), lo, K, (C.c_double * 3)(*origin), ptr(ws), ptr(rec), st))
-    head = torch.cat([rec] + ([] if lines else [table])).cpu().numpy()
+    _capi.check(lib.ot_field_sums(C.byref(R), flat, F, k, ptr(key8), lo, K, (C.c_double * 3)(*origin), ptr(ws), ptr(d_rec), st))
+    head = torch.cat([d_rec] + ([] if lines else [table])).cpu().numpy()
     rec, rest = head[:F * K * M].reshape(F, K, M), head[F * K * M:]
     table = table if lines else rest
 
@@ -253,7 +256,7 @@ def analyse(rays, ranges, section: int, origin, bands, z, reference, reference_f
     starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     K_left, starts, edges = _psf.settle_bands(bands, K_set, starts, table)
     if not starts[-1]:
-        return _empty(section, bands, z, **fixed, **kwargs)
+        return None
     # the bands that are left: the lines there are; or the last one, where an int asked for bands over a single wavelength
     keep = slice(K - 1, K) if not lines and K_left < K else slice(0, K_left)
     rec = rec[:, keep]
@@ -262,14 +265,40 @@ def analyse(rays, ranges, section: int, origin, bands, z, reference, reference_f
         band_wl = table[1:1 + K_left] if lines else rec[:, :, 6].sum(axis=0) / W
         if reference is None:
             reference = rec[:, :, 6].sum() / W.sum()
-    ref = _chromatic.reference_band(band_wl, rec[:, :, 1].sum(axis=0), reference)
+    front = _Front()
+    front.R, front.flat, front.F, front.lo, front.key8, front.K, front.d_rec = R, flat, F, lo, key8, K, d_rec
+    front.keep, front.rec, front.origin, front.edges, front.reference = keep, rec, origin, edges, reference
+    front.reference_band = _chromatic.reference_band(band_wl, rec[:, :, 1].sum(axis=0), reference)
+    return front
+
+
+def default_plane(front, reference_field: int, section: int, sources, field, power) -> float:
+    """z of the plane the analyses compare on where none is given: the `focus_rms` of (reference field, reference band)."""
+    ref = front.reference_band
+    probe = FieldAnalysis(front.rec, front.origin, 0.0, ref, reference_field, section, sources, field, power, None, front.edges)
+    z = float(probe.focus_rms[reference_field, ref]) if ref >= 0 else np.nan
+    if not np.isfinite(z):
+        raise RuntimeError("The rays of the reference field and band have no focus (a collimated bundle, a single ray, no ray?): "
+                           "pass `z`.")
+    return z
+
+
+def analyse(rays, ranges, section: int, origin, bands, z, reference, reference_field: int, sources, field, power, positions,
+            tangents, matrix_at, axis=(0.0, 0.0), **kwargs) -> FieldAnalysis:
+    """Figures of the fields `ranges` [(first, count), ...] of the storage `rays` in section `section`; origin: the point the device
+    refers the lines to; bands, z, reference as `check_arguments` returned them; sources, field, power, positions (relative to the
+    optical axis `axis`), tangents: per field, what `FieldAnalysis` and `paraxial_images` take; matrix_at: see `paraxial_images`.  Reads the
+    p, w and wl planes only.  Reads of the device: those of `band_records`.  The default `reference` is the power-weighted mean
+    wavelength of the rays in the sums."""
+    fixed = dict(origin=origin, reference_field=reference_field, sources=sources, field=field, power=power, axis=axis)
+    front = band_records(rays, ranges, section, origin, bands, reference)
+    if front is None:
+        return _empty(section, bands, z, **fixed, **kwargs)
+    rec, origin, edges, ref = front.rec, front.origin, front.edges, front.reference_band
     if z is None:
-        probe = FieldAnalysis(rec, origin, 0.0, ref, reference_field, section, sources, field, power, None, edges)
-        z = float(probe.focus_rms[reference_field, ref]) if ref >= 0 else np.nan
-        if not np.isfinite(z):
-            raise RuntimeError("The rays of the reference field and band have no focus (a collimated bundle, a single ray, no ray?): "
-                               "pass `z`.")
+        z = default_plane(front, reference_field, section, sources, field, power)
     with np.errstate(invalid="ignore", divide="ignore"):
+        W = rec[:, :, 0].sum(axis=0)
         mean_wl = np.where(rec[:, :, 1].sum(axis=0) > 0, rec[:, :, 6].sum(axis=0) / W, np.nan)
     parax = paraxial_images(matrix_at, mean_wl, positions, tangents, z) + np.asarray(axis, dtype=np.float64)
     return FieldAnalysis(rec, origin, z, ref, reference_field, section, sources, field, power, parax, edges, axis, **kwargs)

@@ -43,6 +43,8 @@ from . import chromatic as _chromatic
 from .chromatic import ChromaticAnalysis
 from . import field as _field
 from .field import FieldAnalysis
+from . import mtf as _mtf
+from .mtf import MTFAnalysis
 from . import fans as _fans
 from .fans import RayFans
 from .geometry.ray_source import RaySource
@@ -911,6 +913,22 @@ class Raytracer(Group):
         table = SectionTable(self)
         sources, bands, z, reference = _field.check_arguments(table.nt, len(self.ray_sources), sources, section, bands, z, reference,
                                                               reference_field, paraxial)
+        ranges, k, axis, positions, tangents, field, power = self._field_points(table, sources, section)
+
+        def matrix_at(wl, z_g, z_b):
+            try:
+                return self.tma(wl).matrix_at(z_g, z_b)
+            except Exception:  # (no lenses, no symmetry, a plane inside a lens: no paraxial image, which the result says with NaN)
+                return None
+
+        return _field.analyse(self.rays, ranges, k, table.origin(k, None), bands, z, reference, reference_field, sources, field,
+                              power, positions, tangents, matrix_at if paraxial == "tma" else None, axis,
+                              long_desc=f"Field analysis of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
+
+    def _field_points(self, table: SectionTable, sources, section):
+        """What the analyses per field point share, after their argument checks: the device, current rays, and per chosen source
+        its ray range, its position relative to the optical axis, its direction tangents (NaN without a constant orientation),
+        its field vector and its power.  -> (ranges, k, axis, positions, tangents, field, power)"""
         require_device()  # (said before anything about the rays: without a device there are none)
         ranges = []
         for s in sources:
@@ -929,16 +947,26 @@ class Raytracer(Group):
             tangents.append(tan)
             field.append(pos[:2] if np.any(pos[:2] != 0) else tan)
             power.append(float(rs.power))
+        return ranges, k, axis, positions, tangents, field, power
 
-        def matrix_at(wl, z_g, z_b):
-            try:
-                return self.tma(wl).matrix_at(z_g, z_b)
-            except Exception:  # (no lenses, no symmetry, a plane inside a lens: no paraxial image, which the result says with NaN)
-                return None
-
-        return _field.analyse(self.rays, ranges, k, table.origin(k, None), bands, z, reference, reference_field, sources, field,
-                              power, positions, tangents, matrix_at if paraxial == "tma" else None, axis,
-                              long_desc=f"Field analysis of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
+    def mtf_analysis(self, sources=None, section: int = None, bands="lines", frequencies=None, z: float = None, dz=None,
+                     reference: float = None, reference_field: int = 0) -> MTFAnalysis:
+        """Geometric MTF across the field and through focus, no counterpart in optrace: every chosen ray source is a field point,
+        and per field point, band of wavelengths, plane and spatial frequency the contrast along the tangential direction of the
+        field and across it is reduced on the GPU in one call, from the position, weight and wavelength planes of one section
+        (mtf.py); the result adds the bands to the polychromatic MTF of every field and finds the through-focus peak.
+        sources, section, bands, reference, reference_field, z: as for `field_analysis`, z by default the best-RMS focus of the
+        reference field in the reference band; dz: None for the plane z alone or 1 to 65 strictly increasing offsets, the planes
+        lie at z + dz; frequencies: 1 to 64 values of 0 or above in cycles per mm, default 17 equal steps from 0 to one over the
+        RMS radius of the reference field in the reference band on the plane z."""
+        table = SectionTable(self)
+        sources, bands, z, reference = _field.check_arguments(table.nt, len(self.ray_sources), sources, section, bands, z, reference,
+                                                              reference_field, None)
+        frequencies, dz = _mtf.check_arguments(frequencies, dz)
+        ranges, k, axis, positions, tangents, field, power = self._field_points(table, sources, section)
+        return _mtf.analyse(self.rays, ranges, k, table.origin(k, None), bands, frequencies, z, dz, reference, reference_field, sources,
+                            field, power,
+                            long_desc=f"MTF analysis of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
 
     def ray_fans(self, source_index: int = 0, section: int = None, bands="lines", focus=None, radius: float = None,
                  n_bins: int = 32, slab: float = 0.1, pupil_radius: float = None) -> RayFans:
