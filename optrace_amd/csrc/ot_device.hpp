@@ -868,6 +868,17 @@ OT_HD double medium_n(MD& md, PL pool, float wl32) {
     return __builtin_nan("");
 }
 
+// expf of the Gaussian filter.  Where the result is subnormal (q < ln 2^-126) the device library's expf is faithful but not
+// correctly rounded: it gave 0 for q = -103.609, 0.72 of the smallest subnormal, where libm -- the reference and the host-built
+// line tables -- gives that subnormal, so a ray died on one route and lived on the other.  There the value is formed from
+// expf(q + 32) (the sum is exact, the result normal) times exp(-32) in double and rounded once.
+OT_HD float ot_expf(float q) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (q < -87.33654f) return (float)((double)expf(q + 32.0f) * 1.2664165549094176e-14);
+#endif
+    return expf(q);
+}
+
 // Filter.__call__ filter.py:39 -> transmission_spectrum.py:73-84 -> spectrum.py:81-120
 template <bool TAB = true, class FD, class PL>
 OT_HD double filter_T(FD& f, PL pool, float wl32) {
@@ -885,7 +896,7 @@ OT_HD double filter_T(FD& f, PL pool, float wl32) {
         case OT_T_GAUSSIAN: {  // float32 arithmetic, spectrum.py:113-115 with the tracer's f32 wavelengths
             float d = wl32 - f.mu32;
             float q = -(d * d) / f.den32;
-            T = (double)(f.val32 * expf(q));
+            T = (double)(f.val32 * ot_expf(q));
             break;
         }
         case OT_T_LINES: {

@@ -273,8 +273,15 @@ def test_full_size_properties_double_gauss():
                                           ("mixed_lines", False)])
 def test_discrete_spectrum_tables_equal_formula_path(name, no_pol):
     """Scenes whose sources are all discrete run the SPEC=2 kernel (n, n1/n2, filter T per line from LDS) in
-    ot_generate_and_trace.  It must give bit-identical rays to generating the same rays (same seed) with
-    ot_rays_generate and tracing them with the formula kernel of ot_trace, which the golden tests pin."""
+    ot_generate_and_trace.  For the scenes and lines here it gives bit-identical rays to generating the same rays (same
+    seed) with ot_rays_generate and tracing them with the formula kernel of ot_trace, which the golden tests pin.
+
+    What holds in general (tests/wavelength_cases.py, test_gpu_wavelength_step.py): the host builds the line tables with
+    libm's pow and expf, the formula kernel multiplies powers out and calls the device library's expf.  The two routes are
+    bitwise equal for the models of + - * / sqrt alone (Constant, Abbe, Sellmeier1-5, Handbook of Optics 1 / 2, Data,
+    Function on lines; filters Constant, Rectangle, Data, Function on lines); for Cauchy, Conrady, Schott, Herzberger,
+    Extended / 2 / 3 and the Gaussian filter each route is within its bar of the exact value and the two may differ in
+    the last bits -- test_gpu_wavelength_step.py counts the samples on which they do."""
     import ctypes as C
     import torch
     from optrace_amd._device import ptr, stream_ptr

@@ -14,6 +14,7 @@ from optrace_amd.scene import CompiledScene
 
 import oracle_bridge as ob
 import scenes
+import wavelength_cases as wc
 from helpers import load, assert_close, sparse_to_dense, image_rel_l1
 
 @pytest.fixture(scope="module")
@@ -92,8 +93,19 @@ def test_oracle_transmission(media):
         pool: list = []
         fd = t._desc(pool, None)
         T = ob.filter_T(fd, np.array(pool), media["wl"])
-        rtol = 3e-7 if name.startswith("Gaussian") else 1e-15  # float32 exp in the reference
-        assert_close(T, media[f"T/{name}"], rtol=rtol, atol=1e-7 if name.startswith("Gaussian") else 0, what=name)
+        if not name.startswith("Gaussian"):
+            assert_close(T, media[f"T/{name}"], rtol=1e-15, atol=0, what=name)
+            continue
+        # float32 around one expf (wavelength_cases, THE BARS): oracle and reference are each within the bar of
+        # fl32(val32 exp(q)), q from float32 basic operations and exp to 64 bits here -- in float32 units of T, also where
+        # the filter is inverse (1 - T; the reference rounds that once more, 2^-25)
+        bar = wc.gaussian_bar(load("wavelength_step.npz"))
+        q = wc.gaussian_q(media["wl"], t.mu, t.sig).astype(np.longdouble)
+        truth = (np.longdouble(np.float32(t.val)) * np.exp(q)).astype(np.float32)
+        for what, got in (("oracle", T), ("reference", media[f"T/{name}"])):
+            Tg = (1 - np.asarray(got, dtype=np.float64)) if t.inverse else np.asarray(got, dtype=np.float64)
+            err = np.abs(Tg - truth.astype(np.float64))
+            assert np.all(err <= bar * np.spacing(truth).astype(np.float64) + (2.0 ** -25 if t.inverse else 0)), (name, what, float(err.max()))
 
 
 def test_oracle_observers(media):
