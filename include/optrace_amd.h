@@ -929,6 +929,55 @@ int ot_mtf_sums(const ot_rays* rays, const int64_t* fields, int32_t n_fields, in
                 int32_t n_bands, const double* origin, const double* records, const double* t, const double* zeta, int32_t n_planes,
                 const double* freq, int32_t n_freq, double* workspace, double* sums, void* stream);
 
+/* ---- spot diagrams (Raytracer.spot_diagram; no counterpart in optrace) -------------------------------------------
+ * Per field point, band of wavelengths and plane where the ray lines of section `section` land about a centre: a power map of
+ * n_px x n_px cells, the rays binned and outside it, and the largest and the power-weighted sum of the squared distances from
+ * the centre.  rays, fields, section, key, key_first, n_bands, origin: those of an ot_field_sums call; the used rays, their bands
+ * and their lines origin_xy + a + (z - origin_z) m are the ones of that call, formed by the same operations, and a used ray with
+ * d_z == 0 (slot 7 of that call's record) enters nothing.  centre[n_fields][n_bands][n_planes][2] DEVICE: the point every tile is
+ * taken about, relative to origin_xy; zeta[n_planes] HOST: the plane's z minus origin_z.  For a ray of field f and band b on
+ * plane j, every line one f64 operation per component and no fused product:
+ *    x = a + zeta_j m          e = x - centre[f][b][j]
+ *    scale = (double)n_px / size          half = 0.5 * n_px
+ *    column = floor(e_x * scale + half)   row = floor(e_y * scale + half)
+ * The ray is binned when column and row both lie in [0, n_px): maps[f][b][j][row][column] += w and counts[f][b][j][0] += 1.
+ * Otherwise -- a value that is no number included -- counts[f][b][j][1] += 1 and outside_power[f][b][j] += w; nothing is clamped
+ * into the map.  A ray with e = -size / 2 exactly lies in cell 0, one with e = +size / 2 exactly outside.  size: the side of every
+ * tile, the same for all.  maps (f64), counts (64 bits, unsigned) and outside_power (f64) are accumulated into: the caller zeroes
+ * them.  The sums of the maps and of outside_power depend on the order of arrival (f64 atomics); the counts do not.
+ * ot_spotdiag_extent: ext[f][b][j] = (max |e|^2, sum w |e|^2), |e|^2 = e_x e_x + e_y e_y, over the same rays; a cell without a ray
+ * gets zeros; a ray whose |e|^2 is no number is skipped by the maximum and turns the sum into no number.  The values of a field
+ * are folded in an order fixed by its count and (n_bands, n_planes) alone: the same call returns the same bits, and a field's
+ * values do not depend on the other fields.  workspace >= ot_spotdiag_workspace(fields, n_fields, n_bands, n_planes) doubles (0
+ * for arguments out of range): per field a list of partials as long as the longest field's; a workgroup takes KB =
+ * min(n_bands, 4) bands side by side and TILE = 8 / KB planes, 3 for KB = 3, and writes a partial of KB * 2 * TILE doubles; a field
+ * has a workgroup per 256 rays, at most max(OT_SD_MIN_BLOCKS, OT_SD_BLOCKS / (groups * tiles)) per 2^28 rays.
+ * ot_spotdiag_maps: a workgroup holds a chunk of T = OT_SD_LDS_BYTES / (8 n_px^2 + 40) whole (band, plane) tiles of a field in
+ * LDS, K Z at the most, and the K Z tiles go in ot_spotdiag_chunks(n_bands, n_planes, n_px) = ceil(K Z / T) chunks; where T is 0
+ * the cells are added to `maps` directly, in one chunk (ot_spotdiag_chunks: 1; 0 for arguments out of range).
+ * All launches are queued on `stream` without a host round trip, and nothing is waited for.  Neither pass reads the direction,
+ * index or polarisation planes.
+ * A null argument, a ray range outside the storage, a field with rays that starts before key_first, a section out of range,
+ * origin or zeta not finite, a size that is not finite or not above 0: OT_ERR_INVALID; n_fields outside 1 .. OT_FIELD_MAX_FIELDS,
+ * n_bands outside 1 .. OT_CHROM_MAX_BANDS, n_planes outside 1 .. OT_MTF_MAX_PLANES, n_px outside 1 .. OT_SD_MAX_PX or
+ * n_fields n_bands n_planes n_px^2 above OT_SD_MAX_CELLS: OT_ERR_UNSUPPORTED, both before a device is looked for; no ray in any
+ * field returns OT_OK without a launch and leaves the outputs alone. */
+#define OT_SD_MAX_PX 1024
+#define OT_SD_MAX_CELLS ((int64_t)1 << 28)
+#define OT_SD_BLOCKS 1024          /* extent pass: workgroups per field and 2^28 rays over all groups of bands and tiles, about */
+#define OT_SD_MIN_BLOCKS 16        /* ... and the fewest the largest fields are walked by */
+#define OT_SD_LDS_BYTES (159 * 1024) /* map pass: dynamic LDS of a workgroup at the most, one workgroup of 1024 lanes per CU */
+#define OT_SD_MAP_BLOCKS 512       /* map pass: workgroups per field and 2^28 rays over all chunks, about */
+#define OT_SD_MAP_MIN_BLOCKS 4     /* ... and the fewest the largest fields are walked by */
+int64_t ot_spotdiag_workspace(const int64_t* fields, int32_t n_fields, int32_t n_bands, int32_t n_planes);
+int32_t ot_spotdiag_chunks(int32_t n_bands, int32_t n_planes, int32_t n_px);
+int ot_spotdiag_extent(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key,
+                       int64_t key_first, int32_t n_bands, const double* origin, const double* centre, const double* zeta,
+                       int32_t n_planes, double* workspace, double* ext, void* stream);
+int ot_spotdiag_maps(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key,
+                     int64_t key_first, int32_t n_bands, const double* origin, const double* centre, const double* zeta,
+                     int32_t n_planes, int32_t n_px, double size, double* maps, uint64_t* counts, double* outside_power, void* stream);
+
 /* ---- ray fans (Raytracer.ray_fans; no counterpart in optrace) ----------------------------------------------------
  * Per band of wavelengths the transverse ray aberration and the optical path difference along two cuts of the pupil, from the
  * dense planes u, v, opl, w_out that ot_wavefront_paths left for the rays [first, first + count) and the moments record of

@@ -24,6 +24,7 @@ from .footprint import Footprints
 from .chromatic import ChromaticAnalysis
 from .field import FieldAnalysis
 from .mtf import MTFAnalysis
+from .spot_diagram import SpotDiagram
 from .fans import RayFans
 from .ray_storage import RayStorage
 from .raytracer import Raytracer

@@ -45,6 +45,8 @@ from . import field as _field
 from .field import FieldAnalysis
 from . import mtf as _mtf
 from .mtf import MTFAnalysis
+from . import spot_diagram as _spot_diagram
+from .spot_diagram import SpotDiagram
 from . import fans as _fans
 from .fans import RayFans
 from .geometry.ray_source import RaySource
@@ -967,6 +969,27 @@ class Raytracer(Group):
         return _mtf.analyse(self.rays, ranges, k, table.origin(k, None), bands, frequencies, z, dz, reference, reference_field, sources,
                             field, power,
                             long_desc=f"MTF analysis of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
+
+    def spot_diagram(self, sources=None, section: int = None, bands="lines", z: float = None, dz=None, n_px: int = 64,
+                     size: float = None, centre="centroid", reference: float = None, reference_field: int = 0) -> SpotDiagram:
+        """Spot diagrams across the field and through focus, no counterpart in optrace: every chosen ray source is a field point,
+        and per field point, band of wavelengths and plane the rays are binned on the GPU in one call into a power map of n_px x
+        n_px cells about a centre, all tiles at one common scale, from the position, weight and wavelength planes of one section
+        (spot_diagram.py); with the rays outside a tile, their power, and the largest and the RMS distance from the centre.
+        sources, section, bands, reference, reference_field, z: as for `field_analysis`; dz: as for `mtf_analysis`; n_px: 1 to
+        1024 cells per side; size: the side of every tile in mm, default slightly above twice the largest distance of any ray
+        from the centre of its tile; centre: what every tile is drawn about, per field and plane -- "centroid": the
+        power-weighted mean of the rays of all bands, "band": each band's own centroid, "reference": the centroid of the
+        reference band, or an array (F, 2) of absolute points, the same on every plane."""
+        table = SectionTable(self)
+        sources, bands, z, reference = _field.check_arguments(table.nt, len(self.ray_sources), sources, section, bands, z, reference,
+                                                              reference_field, None)
+        _, dz = _mtf.check_arguments(None, dz)
+        n_px, size, centre = _spot_diagram.check_arguments(n_px, size, centre, len(sources))
+        ranges, k, axis, positions, tangents, field, power = self._field_points(table, sources, section)
+        return _spot_diagram.analyse(self.rays, ranges, k, table.origin(k, None), bands, z, dz, n_px, size, centre, reference,
+                                     reference_field, sources, field, power,
+                                     long_desc=f"Spot diagram of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
 
     def ray_fans(self, source_index: int = 0, section: int = None, bands="lines", focus=None, radius: float = None,
                  n_bins: int = 32, slab: float = 0.1, pupil_radius: float = None) -> RayFans:
