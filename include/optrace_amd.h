@@ -978,6 +978,57 @@ int ot_spotdiag_maps(const ot_rays* rays, const int64_t* fields, int32_t n_field
                      int64_t key_first, int32_t n_bands, const double* origin, const double* centre, const double* zeta,
                      int32_t n_planes, int32_t n_px, double size, double* maps, uint64_t* counts, double* outside_power, void* stream);
 
+/* ---- wavefront across the field (Raytracer.wavefront_field; no counterpart in optrace) ----------------------------
+ * Per field point and band of wavelengths -- a cell -- the wavefront analysis above: the sums for a reference sphere, the optical
+ * path of every ray to the sphere of its cell, the moments of the paths and the normal equations of a Zernike fit.  fields, key,
+ * key_first, section, n_bands and the used rays: those of ot_field_sums; rays that are not used and rays in no band are not read
+ * into arithmetic.  The dense planes u, v, opl (f64), w_out (f32) and the wl handed to ot_wavefield_moments start at ray
+ * key_first, as key does: entry r - key_first belongs to ray r, and entries of no field are left alone.  All arithmetic in f64.
+ * Pointers are DEVICE unless said otherwise; every entry queues its launches on `stream` without a host round trip, and nothing
+ * is waited for.
+ * ot_wavefield_focus: sums[n_fields][n_bands][OT_WF_FOCUS_M], per cell the sums of ot_wavefront_focus over its used rays, with
+ *   q = p[section] - origin, origin[3] HOST.  Reads key, p and w.
+ * ot_wavefield_paths: spheres[n_fields][n_bands][4] = (c_x, c_y, c_z, R) per cell; a cell has a sphere when all four are finite
+ *   and R != 0.  A used ray of a cell with a sphere gets opl, (u, v) and w_out by the step of ot_wavefront_paths with (c, R):
+ *   the same device function, so the same bits as that call with that sphere.  Every other ray of a field gets w_out = 0 and NaN
+ *   elsewhere.  counts[n_fields][n_bands][2] (int64; zeroed here): used rays of the cell whose line misses its sphere | used
+ *   rays of a cell without a sphere.  Reads key, p, w and n.
+ * ot_wavefield_moments: an entry counts when its key is a band and w_out > 0.  moments[n_fields][n_bands][OT_WFF_M] =
+ *    0 sum w   1 entries   2 sum w opl   3 sum w u   4 sum w v   5 sum w wl   6 min opl   7 max opl
+ *    8 sum w (opl - slot 2 / slot 0)^2, the difference formed before squaring: a second pass over the planes
+ *   a cell without an entry: slots 0 .. 7 are 0 and slot 8 is NaN.  pupil[n_fields][OT_WFF_PUPIL_M], common to the bands of a
+ *   field: the centre (sum_b slot 3, sum_b slot 4) / sum_b slot 0, added in band order | the largest squared distance of the
+ *   field's entries from it (0 without an entry) | its root, the pupil radius.
+ * ot_wavefield_zernike: out[n_fields][n_bands][J (J + 1) / 2 + J], per cell the layout of ot_wavefront_zernike, Z at
+ *   (x, y) = ((u, v) - the field's centre) / pupil radius by the same polynomial code, opl against the cell's mean.
+ *   pupil_radius NaN: pupil[f][3]; otherwise entries with x^2 + y^2 > 1 are left out.  1 <= J <= OT_WF_MAX_J.  A cell without
+ *   an entry: zeros.
+ * focus and moments request every ray's data once, whatever n_fields and n_bands are: the key byte of every ray of a field and
+ * the data of a ray with a band; paths likewise, one thread per ray.  zernike requests a field's key bytes once per band and
+ * chunk of the triangle ((JT + 1) / 2 chunks, JT = 15 or 36) and an entry's planes once per chunk.  The sums of a field are
+ * added in an order fixed by its count, n_bands and J alone and without f64 atomics: the same call returns the same bits, and
+ * a field's outputs do not depend on the other fields.
+ * A null argument, a ray range outside the storage, a field with rays that starts before key_first, a section out of range,
+ * origin not finite, J below 1, a pupil radius that is neither NaN nor finite and above 0: OT_ERR_INVALID; n_fields outside
+ * 1 .. OT_FIELD_MAX_FIELDS, n_bands outside 1 .. OT_CHROM_MAX_BANDS, J above OT_WF_MAX_J: OT_ERR_UNSUPPORTED, both before a
+ * device is looked for; no ray in any field returns OT_OK without a launch and leaves the outputs alone.
+ * workspace >= ot_wavefield_workspace(fields, n_fields, n_bands, J) doubles, for every entry (0 for arguments out of range). */
+#define OT_WFF_M 9
+#define OT_WFF_PUPIL_M 4
+#define OT_WFF_FIT_BLOCKS 64 /* most workgroups per field, 2^28 rays, band and chunk whose partial sums of the fit the workspace holds */
+int64_t ot_wavefield_workspace(const int64_t* fields, int32_t n_fields, int32_t n_bands, int32_t J);
+int ot_wavefield_focus(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key,
+                       int64_t key_first, int32_t n_bands, const double* origin, double* workspace, double* sums, void* stream);
+int ot_wavefield_paths(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key,
+                       int64_t key_first, int32_t n_bands, const double* spheres, double* u, double* v, double* opl, float* w_out,
+                       int64_t* counts, void* stream);
+int ot_wavefield_moments(const int64_t* fields, int32_t n_fields, const double* u, const double* v, const double* opl, const float* w,
+                         const float* wl, const uint8_t* key, int64_t key_first, int32_t n_bands, double* workspace, double* moments,
+                         double* pupil, void* stream);
+int ot_wavefield_zernike(const int64_t* fields, int32_t n_fields, const double* u, const double* v, const double* opl, const float* w,
+                         const uint8_t* key, int64_t key_first, int32_t n_bands, const double* moments, const double* pupil,
+                         double pupil_radius, int32_t J, double* workspace, double* out, void* stream);
+
 /* ---- ray fans (Raytracer.ray_fans; no counterpart in optrace) ----------------------------------------------------
  * Per band of wavelengths the transverse ray aberration and the optical path difference along two cuts of the pupil, from the
  * dense planes u, v, opl, w_out that ot_wavefront_paths left for the rays [first, first + count) and the moments record of

@@ -25,6 +25,7 @@ from .chromatic import ChromaticAnalysis
 from .field import FieldAnalysis
 from .mtf import MTFAnalysis
 from .spot_diagram import SpotDiagram
+from .wavefront_field import WavefrontField
 from .fans import RayFans
 from .ray_storage import RayStorage
 from .raytracer import Raytracer

@@ -217,6 +217,11 @@ SIGNATURES = {
                                      C.POINTER(C.c_double), i32, vp, vp, vp]),
     "ot_spotdiag_maps": (C.c_int, [C.POINTER(Rays), C.POINTER(i64), i32, i32, vp, i64, i32, C.POINTER(C.c_double), vp,
                                    C.POINTER(C.c_double), i32, i32, C.c_double, vp, vp, vp, vp]),
+    "ot_wavefield_workspace": (i64, [C.POINTER(i64), i32, i32, i32]),
+    "ot_wavefield_focus": (C.c_int, [C.POINTER(Rays), C.POINTER(i64), i32, i32, vp, i64, i32, C.POINTER(C.c_double), vp, vp, vp]),
+    "ot_wavefield_paths": (C.c_int, [C.POINTER(Rays), C.POINTER(i64), i32, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ot_wavefield_moments": (C.c_int, [C.POINTER(i64), i32, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
+    "ot_wavefield_zernike": (C.c_int, [C.POINTER(i64), i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, C.c_double, i32, vp, vp, vp]),
     "ot_fans_workspace": (i64, [i64, i32]),
     "ot_fans_transverse": (C.c_int, [C.POINTER(Rays), i64, i64, i32, C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
     "ot_fans_bands": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
@@ -251,6 +256,7 @@ WF_FOCUS_M, WF_M, WF_MAX_J, WF_MAX_GRID, WF_WS = 17, 11, 36, 1024, 40 * 2048  # 
 FP_M, FP_MAX_PX = 17, 1024  # OT_FP_*
 CHROM_M, CHROM_MAX_BANDS, CHROM_BLOCKS, CHROM_NO_BAND = 10, 32, 1024, 255  # OT_CHROM_*; the key of a ray in no band
 FIELD_M, FIELD_MAX_FIELDS, FIELD_BLOCKS = 18, 64, 1024  # OT_FIELD_*
+WFF_M, WFF_PUPIL_M, WFF_FIT_BLOCKS = 9, 4, 64  # OT_WFF_*
 MTF_MAX_FREQ, MTF_MAX_PLANES, MTF_BLOCKS, MTF_MIN_BLOCKS = 64, 65, 1024, 16  # OT_MTF_*
 SD_MAX_PX, SD_MAX_CELLS, SD_BLOCKS, SD_MIN_BLOCKS, SD_LDS_BYTES = 1024, 1 << 28, 1024, 16, 159 * 1024  # OT_SD_*
 FAN_M, FAN_BIN_M, FAN_MAX_BINS = 13, 6, 256  # OT_FAN_*

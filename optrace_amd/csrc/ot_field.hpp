@@ -13,6 +13,7 @@
 #include "ot_block_reduce.hpp"
 #include "ot_device.hpp"
 #include "ot_field_ray.hpp"
+#include "ot_field_roles.hpp"
 
 // slots of the record (include/optrace_amd.h, ot_field_sums): pass 1 carries the first FD_M1 of them, pass 2 the rest
 enum { FD_W = 0, FD_COUNT, FD_WAX, FD_WAY, FD_WMX, FD_WMY, FD_WWL, FD_PARALLEL, FD_M1,
@@ -20,86 +21,7 @@ enum { FD_W = 0, FD_COUNT, FD_WAX, FD_WAY, FD_WMX, FD_WMY, FD_WWL, FD_PARALLEL, 
 static_assert(FD_M == OT_FIELD_M && FD_M1 == 8, "the record of the header");
 #define FD_M2 (FD_M - FD_M1)
 
-// One launch takes up to FD_PIECES pieces; a piece is a field's range, or 2^28 rays of it: 32-bit offsets from `base`.
-#define FD_PIECES 64
-struct FdPiece {
-    int64_t base;     // first ray of the piece in the storage
-    uint32_t n;       // its rays, at most 2^28
-    uint32_t blocks;  // workgroups that walk it
-    uint32_t block0;  // place of its first workgroup's partial in the field's list
-    uint32_t field;   // bits 0 .. 30 the field; bit 31: the field's last piece, which zeroes the rest of the list
-};
-struct FdBatch {
-    FdPiece piece[FD_PIECES];
-};
-
-// The band sums of a wave.  The lanes change roles: lane (t, j) = (lane / J, lane % J), J = 64 / M, owns slot t of the bands
-// j, j + J, ..., NC of them, in registers for the whole walk.  Per step every lane puts the M values of its ray into the wave's
-// stage in LDS; then the wave goes through its rays of a band in lane order (a wave-uniform loop over the ballot), and the owner
-// of (slot, band of the ray) adds the staged value: one addition per slot and ray whatever the number of bands, each sum a chain
-// in the order of the rays.  stage[M][65]: a row per slot, one double of padding between rows.
-template <int M>
-struct FdRoles {
-    static constexpr int J = 64 / M;
-};
-#define FD_STAGE 65
-
-template <int M, int NC>
-OT_DEV void fd_add_rays(unsigned kb, const double (&v)[M], double (*stage)[FD_STAGE], double (&acc)[NC]) {
-    constexpr int J = FdRoles<M>::J;
-    const unsigned lane = threadIdx.x & 63, t = lane / J < M ? lane / J : M - 1, j = lane % J;
-    const bool owner = lane < M * J;
-    __builtin_amdgcn_wave_barrier();  // (the reads of the step before are done: the wave runs in step, LDS takes its requests in order)
-#pragma unroll
-    for (int m = 0; m < M; m++) stage[m][lane] = v[m];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    unsigned long long pending = __ballot(kb != FD_NO_BAND);
-    while (pending) {  // (wave-uniform: a ballot)
-        const int i = __ffsll((long long)pending) - 1;
-        pending &= pending - 1;
-        const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)kb, i);  // (wave-uniform)
-        const double x = (owner && b % J == j) ? stage[t][i] : 0.0;
-        const unsigned c = b / J;
-#pragma unroll
-        for (int n = 0; n < NC; n++)
-            if (c == (unsigned)n) acc[n] += x;  // (a wave-uniform choice; x + 0 changes no bit)
-    }
-}
-
-// the lanes' sums -> the wave's acc[K][M] in LDS
-template <int M, int NC>
-OT_DEV void fd_store_roles(const double (&acc)[NC], unsigned K, double (*out)[M]) {
-    constexpr int J = FdRoles<M>::J;
-    const unsigned lane = threadIdx.x & 63, t = lane / J, j = lane % J;
-    if (lane >= M * J) return;
-#pragma unroll
-    for (int n = 0; n < NC; n++)
-        if (j + n * J < K) out[j + n * J][t] = acc[n];
-}
-
-// acc[waves][K][SLOTS] in LDS -> part[K][SLOTS], the waves in their order
-template <int SLOTS>
-OT_DEV void fd_write_partial(const double (*acc)[OT_CHROM_MAX_BANDS][SLOTS], unsigned K, double* __restrict__ part) {
-    __syncthreads();
-    for (unsigned t = threadIdx.x; t < K * SLOTS; t += OT_RED_THREADS) {
-        const unsigned b = t / SLOTS, m = t % SLOTS;
-        double r = acc[0][b][m];
-        for (int wv = 1; wv < OT_RED_WAVES; wv++) r += acc[wv][b][m];
-        part[t] = r;
-    }
-}
-
-// A workgroup beyond its piece's: nothing to walk.  Those of a field's last piece fill the rest of the field's list with zeros,
-// which the last kernel adds without changing a bit of the sums.  -> true: the workgroup has rays.
-OT_DEV bool fd_my_piece(const FdPiece& P, unsigned list_len, unsigned cell, double* __restrict__ part_field) {
-    if (blockIdx.x < P.blocks) return true;
-    const unsigned at = P.block0 + blockIdx.x;
-    if ((P.field >> 31) && at < list_len)
-        for (unsigned t = threadIdx.x; t < cell; t += OT_RED_THREADS) part_field[(int64_t)at * cell + t] = 0.0;
-    return false;
-}
+// (the piece list of a launch and the lanes' second role, fd_add_rays: ot_field_roles.hpp)
 
 // part[F][list_len][K][FD_M1]; grid (list_len, pieces of the batch).  NC: bands a lane owns, NC * (64 / FD_M1) >= K
 template <int NC>

@@ -60,29 +60,10 @@ __global__ __launch_bounds__(OT_RED_THREADS) void wf_paths_kernel(ot_rays R, int
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool miss = false;
     if (i < count) {
-        const int64_t r = first + i, N = R.N;
-        const double nan = __builtin_nan("");
-        double ui = nan, vi = nan, li = nan;
-        float wi = 0.f;
-        if (R.w[r + N * k] > 0.f) {
-            V3 p0 = wf_position(R, r, 0);
-            double sum = 0.0;
-            for (int j = 0; j < k; j++) {  // ascending j, as the definition says
-                const V3 p1 = wf_position(R, r, j + 1);
-                const double dx = p1.x - p0.x, dy = p1.y - p0.y, dz = p1.z - p0.z;
-                sum += R.n[r + N * j] * ot_sqrt(dx * dx + dy * dy + dz * dz);
-                p0 = p1;
-            }
-            const WfSphere h = wf_sphere(R, r, k, p0, cx, cy, cz, radius);
-            if (h.hit) {
-                const double ax = fabs(radius);
-                li = sum + R.n[r + N * k] * h.t;
-                ui = h.h.x / ax;
-                vi = h.h.y / ax;
-                wi = (float)h.w;
-            }
-            miss = h.used && !h.hit;
-        }
+        double ui, vi, li;
+        float wi;
+        const int64_t r = first + i;
+        miss = wf_path(R, r, k, cx, cy, cz, radius, ui, vi, li, wi);
         u[i] = ui;
         v[i] = vi;
         opl[i] = li;
@@ -180,67 +161,7 @@ __global__ __launch_bounds__(1024) void wf_map_kernel(int64_t n, const double* _
     }
 }
 
-// ---- Zernike polynomials, Noll's order -------------------------------------------------------------------------------
-// Z_j = N_n^m R_n^|m|(rho) cos(m theta) for even j, sin(|m| theta) for odd j, 1 for m = 0.  rho^m cos / sin (m theta) are the
-// real and imaginary parts of (x + i y)^m, and R_n^m / rho^m is a polynomial in rho^2 whose coefficients, times the norm, are
-// compile-time constants: no trigonometry, no division, no special case at the centre.
-constexpr int wf_noll_n(int j) {  // radial order of Z_j, j from 1
-    int n = 0;
-    while ((n + 1) * (n + 2) / 2 < j) n++;
-    return n;
-}
-constexpr int wf_noll_m(int j) {  // azimuthal order |m|
-    const int n = wf_noll_n(j), p = j - n * (n + 1) / 2 - 1;
-    return n % 2 ? 2 * (p / 2) + 1 : 2 * ((p + 1) / 2);
-}
-constexpr double wf_factorial(int k) { return k < 2 ? 1.0 : k * wf_factorial(k - 1); }
-// coefficient of rho^(n - 2 i) in R_n^m
-constexpr double wf_radial_coeff(int n, int m, int i) {
-    return (i % 2 ? -1.0 : 1.0) * wf_factorial(n - i) / (wf_factorial(i) * wf_factorial((n + m) / 2 - i) * wf_factorial((n - m) / 2 - i));
-}
-// sqrt(n + 1) and sqrt(2 n + 2), n = 0 .. 7
-constexpr double wf_norm0[8] = {1.0, 1.4142135623730951, 1.7320508075688772, 2.0, 2.23606797749979, 2.449489742783178,
-                                2.6457513110645907, 2.8284271247461903};
-constexpr double wf_normm[8] = {1.4142135623730951, 2.0, 2.449489742783178, 2.8284271247461903, 3.1622776601683795,
-                                3.4641016151377544, 3.7416573867739413, 4.0};
-
-template <int J>
-struct WfZernikeTerm {
-    static constexpr int n = wf_noll_n(J), m = wf_noll_m(J), deg = (n - m) / 2;
-    static constexpr double norm = m ? wf_normm[n] : wf_norm0[n];
-    // norm times the coefficients of R_n^m / rho^m, highest power of t = rho^2 first (at most four: n <= 7); constants of the
-    // class, so that the compiler holds numbers and no calls
-    static constexpr double c0 = norm * wf_radial_coeff(n, m, 0), c1 = deg >= 1 ? norm * wf_radial_coeff(n, m, 1) : 0.0,
-                            c2 = deg >= 2 ? norm * wf_radial_coeff(n, m, 2) : 0.0, c3 = deg >= 3 ? norm * wf_radial_coeff(n, m, 3) : 0.0;
-    static_assert(deg <= 3, "radial orders up to 7");
-    // cm[i], sm[i]: real and imaginary part of (x + i y)^i; t = x^2 + y^2
-    static OT_DEV double eval(const double (&cm)[8], const double (&sm)[8], double t) {
-        double r = c0;
-        if constexpr (deg >= 1) r = r * t + c1;
-        if constexpr (deg >= 2) r = r * t + c2;
-        if constexpr (deg >= 3) r = r * t + c3;
-        return r * (m == 0 ? 1.0 : J % 2 ? sm[m] : cm[m]);
-    }
-};
-template <int JT, int J = 1>
-struct WfZernikeAll {
-    static OT_DEV void eval(double (&Z)[JT], const double (&cm)[8], const double (&sm)[8], double t) {
-        Z[J - 1] = WfZernikeTerm<J>::eval(cm, sm, t);
-        if constexpr (J < JT) WfZernikeAll<JT, J + 1>::eval(Z, cm, sm, t);
-    }
-};
-template <int JT>
-OT_DEV void wf_zernike_all(double x, double y, double (&Z)[JT]) {
-    double cm[8], sm[8];
-    cm[0] = 1.0;
-    sm[0] = 0.0;
-#pragma unroll
-    for (int i = 1; i < 8; i++) {
-        cm[i] = cm[i - 1] * x - sm[i - 1] * y;
-        sm[i] = cm[i - 1] * y + sm[i - 1] * x;
-    }
-    WfZernikeAll<JT>::eval(Z, cm, sm, x * x + y * y);
-}
+// (the Zernike polynomials in Noll's order, wf_zernike_all: ot_wavefront_ray.hpp)
 
 // Normal equations for the first JT polynomials, JT the table size at or above the caller's J.  Workgroup (bx, c) walks the list
 // as workgroup bx of gridDim.x for chunk c < (JT + 1) / 2: rows a = c and b = JT - 1 - c of the upper triangle, JT + 1 entries of

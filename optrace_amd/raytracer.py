@@ -47,6 +47,8 @@ from . import mtf as _mtf
 from .mtf import MTFAnalysis
 from . import spot_diagram as _spot_diagram
 from .spot_diagram import SpotDiagram
+from . import wavefront_field as _wavefront_field
+from .wavefront_field import WavefrontField
 from . import fans as _fans
 from .fans import RayFans
 from .geometry.ray_source import RaySource
@@ -990,6 +992,32 @@ class Raytracer(Group):
         return _spot_diagram.analyse(self.rays, ranges, k, table.origin(k, None), bands, z, dz, n_px, size, centre, reference,
                                      reference_field, sources, field, power,
                                      long_desc=f"Spot diagram of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
+
+    def wavefront_field(self, sources=None, section: int = None, bands="lines", n_zernike: int = 15, sphere: str = "field",
+                        focus=None, radius=None, pupil_radius: float = None, reference: float = None,
+                        reference_field: int = 0) -> WavefrontField:
+        """Wavefront error across the field and the bands of wavelengths, no counterpart in optrace: every chosen ray source is a
+        field point, and per field point and band the optical path difference against a reference sphere, its RMS, extremes and
+        Strehl ratio and the Zernike coefficients of a least-squares fit on a pupil common to the bands of a field are reduced on
+        the GPU in one call (wavefront_field.py).  sources, section, bands, reference, reference_field: as for `field_analysis`;
+        n_zernike: Noll polynomials fitted, 1 to 36; sphere: "field" -- all bands of a field share the sphere of the field's
+        reference band, so that axial colour shows as defocus (Z4) and lateral colour as tilt (Z2, Z3) -- or "band", every cell
+        against its own sphere; the sphere of a cell is that of `wavefront_analysis`, the point closest to its ray lines and its
+        signed distance from their mean start, and a collimated cell has none (its rays are counted in `n_no_sphere`); focus
+        (F, 3), radius (F,) or one number: centre and signed radius per field for all its bands, in place of the found ones;
+        pupil_radius: radius of the unit disc in units of |radius|, default per field the largest distance from the pupil
+        centre."""
+        table = SectionTable(self)
+        sources, bands, _, reference = _field.check_arguments(table.nt, len(self.ray_sources), sources, section, bands, None, reference,
+                                                              reference_field, None)
+        focus, radius, pupil_radius = _wavefront_field.check_arguments(len(sources), n_zernike, sphere, focus, radius, pupil_radius)
+        ranges, k, axis, positions, tangents, field, power = self._field_points(table, sources, section)
+        if table.ideal_before(k):
+            warning(f"An ideal lens lies before section {k}: the optical path through an ideal lens is not defined, "
+                    f"the wavefront figures hold up to what it would add.")
+        return _wavefront_field.analyse(self.rays, ranges, k, table.origin(k, None), bands, n_zernike, sphere, focus, radius,
+                                        pupil_radius, reference, reference_field, sources, field,
+                                        long_desc=f"Wavefront of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
 
     def ray_fans(self, source_index: int = 0, section: int = None, bands="lines", focus=None, radius: float = None,
                  n_bins: int = 32, slab: float = 0.1, pupil_radius: float = None) -> RayFans:
