@@ -183,6 +183,8 @@ OT_DEV void observer_xyz_at(const double* obs, double l, double& xo, double& yo,
             yo = (f0[4] - f0[1]) / 1.0 * t + f0[1];
             zo = (f0[5] - f0[2]) / 1.0 * t + f0[2];
         }
+    } else if (l != l) {
+        xo = yo = zo = l;  // np.interp hands a NaN wavelength through
     }
 }
 

@@ -489,9 +489,12 @@ struct RenderArgs {
 #define OT_HASH_EMPTY (-1)
 
 // misc.binning_indices_2d misc.py:75-89: pixel index iy * Nx + ix of a hit, -1 outside (weight 0 in the reference)
+// (a NaN position: the reference's int32 conversion gives INT_MIN, outside; the device's gives 0 -- fmax(NaN, -1) = -1 instead,
+// and every index below -1 is as far outside at -1.  On the other side nothing changes: indices of 2^31 and above and +inf rely
+// on the device's conversion saturating at INT_MAX, which the range test rejects like the reference's INT_MIN)
 OT_DEV int hit_pixel(const RenderArgs& a, double x, double y, int32_t& ix, int32_t& iy) {
-    ix = (int32_t)floor(a.fx * (x - a.x0));
-    iy = (int32_t)floor(a.fy * (y - a.y0));
+    ix = (int32_t)fmax(floor(a.fx * (x - a.x0)), -1.0);
+    iy = (int32_t)fmax(floor(a.fy * (y - a.y0)), -1.0);
     if (y == a.y1) iy = a.Ny - 1;
     if (x == a.x1) ix = a.Nx - 1;
     if (ix < 0 || iy < 0 || iy >= a.Ny || ix >= a.Nx) return -1;
@@ -518,6 +521,8 @@ OT_DEV void observer_xyz_at6(const double* obs6, double l, double& xo, double& y
         xo = a.y * t + a.x;
         yo = b.y * t + b.x;
         zo = c.y * t + c.x;
+    } else if (l != l) {
+        xo = yo = zo = l;  // np.interp hands a NaN wavelength through
     }
 }
 

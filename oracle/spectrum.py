@@ -31,7 +31,16 @@ def render(wl: np.ndarray, w: np.ndarray):
     wl0, wl1 = wl.min(), wl.max()
     if np.abs(wl0 - wl1) < 1:  # light_spectrum.py:73-74
         wl0, wl1 = max(wl0 - 1, WL_RANGE[0]), min(wl0 + 1, WL_RANGE[1])
-    first, last = np.float32(wl0), np.float32(wl1)
+    edges, sums = histogram(wl, w, np.float32(wl0), np.float32(wl1), N)
+    return edges.astype(np.float64), sums * (1 / (float(edges[1]) - float(edges[0])))
+
+
+def histogram(wl: np.ndarray, w: np.ndarray, first: np.float32, last: np.float32, N: int):
+    """(edges f32, sums f64): the weights of float32 wavelengths `wl` summed per bin of the N uniform bins between the
+    float32 values `first` and `last`, the last bin closed on the right, NaN and values outside dropped."""
+    wl = np.asarray(wl, dtype=np.float32)
+    w = np.asarray(w, dtype=np.float32)
+    first, last = np.float32(first), np.float32(last)
     edges = np.linspace(first, last, N + 1, endpoint=True, dtype=np.float32)
     denom = np.float32(last - first)
     sums = np.zeros(N, dtype=np.float64)
@@ -46,4 +55,4 @@ def render(wl: np.ndarray, w: np.ndarray):
         if x >= edges[idx + 1] and idx != N - 1:
             idx += 1
         sums[idx] += float(wi)
-    return edges.astype(np.float64), sums * (1 / (float(edges[1]) - float(edges[0])))
+    return edges, sums
