@@ -1119,6 +1119,45 @@ int ot_psf_stack(int64_t n, const double* rec, int32_t n_bands, const int64_t* s
 int ot_psf_combine(int32_t n_bands, int32_t n_planes, int32_t n_px, const double* field, const double* sums, double* intensity,
                    double* band_strehl, double* strehl, double* g, double* noise_floor, void* stream);
 
+/* The stack for the fields of a field series in one call (Raytracer.huygens_field): cell f n_bands + b holds the rays of field f
+ * in band b, every field has a reference sphere of its own.  Checks and codes as above, with the name of the entry point in
+ * ot_last_error; n_fields above OT_FIELD_MAX_FIELDS: OT_ERR_UNSUPPORTED.
+ * ot_psf_field_rays: rec[OT_PSF_REC * span], entry i ray key_first + i: the record of ot_psf_rays against the sphere
+ *   spheres[f][b][4] = (c, R) and the mean path moments[f][b][2] / moments[f][b][0] (ot_wavefield_moments) of the ray's cell --
+ *   f the field whose range fields[f] = (first, count) (HOST) holds the ray, b = key[i] --, with opl[span] as
+ *   ot_wavefield_paths wrote it.  A ray of no field, a key of n_bands or above, a cell whose sphere holds no number, and the
+ *   rays that ot_wavefield_paths does not use: six zeros.  Every field lies within [key_first, key_first + span).
+ * ot_psf_field_sum: rec[OT_PSF_REC * n] grouped by cell, starts[n_fields * n_bands + 1] HOST, ascending from 0 to n;
+ *   radius[n_fields] HOST, finite and not zero (of a field without a record: any such number).
+ *   field[n_fields][n_planes][n_bands][2][n_px * n_px] and sums[n_fields][n_planes][n_bands][5] as ot_psf_stack forms them per
+ *   band.  One launch over (point tiles, ray chunks, planes): no chunk straddles a cell, a cell without a record owns none, the
+ *   chunk length is that of ot_psf_stack for ceil(n / g) records, g the fields that hold a record, and n_planes planes.  table: OT_PSF_FIELD_TABLE(n_fields * n_bands)
+ *   8-byte words on the DEVICE that the call fills with the cells.  The result is a function of rec, starts, radius, n_px, size
+ *   and dz alone; with one field it is ot_psf_stack's, bit for bit.  workspace >= ot_psf_field_workspace(...) doubles, a bound
+ *   that needs no starts (0 for arguments out of range; with one field ot_psf_stack_workspace); workspace bound plus field above
+ *   OT_PSF_STACK_CAP doubles, or a bound of more than 65535 chunks (the grid's second dimension): OT_ERR_UNSUPPORTED.
+ * ot_psf_field_combine: ot_psf_combine per field: intensity[n_fields][n_planes][n_px * n_px], band_strehl[n_fields][n_planes]
+ *   [n_bands], strehl[n_fields][n_planes], g[n_fields][n_bands], noise_floor[n_fields]; a field without a ray: NaN in intensity,
+ *   strehl and noise_floor.
+ * ot_psf_field_otf: with J = intensity - noise_floor of the field, the pixel centres (x, y) of ot_psf_sum relative to the focus,
+ *   t[n_fields][2] HOST and s = (-t_y, t_x): out[n_fields][n_planes][n_freq][6] = Re, Im of sum_p J_p exp(-2 pi i nu (t . x_p)) |
+ *   Re, Im of the same along s | their moduli over |sum_p J_p|.  frequencies[n_freq] HOST, 1 <= n_freq <= OT_PSFF_MAX_FREQ
+ *   (OT_ERR_UNSUPPORTED above), finite, not below zero and not above n_px / (2 size).  The sums are added in an order fixed by
+ *   n_px alone (csrc/ot_psf_field.hpp). */
+#define OT_PSFF_MAX_FREQ 64
+#define OT_PSF_FIELD_TABLE(cells) (4 * (int64_t)(cells) + 2)
+int64_t ot_psf_field_workspace(int64_t n, int32_t n_fields, int32_t n_bands, int32_t n_px, int32_t n_planes);
+int ot_psf_field_rays(const ot_rays* rays, const int64_t* fields, int32_t n_fields, int32_t section, const uint8_t* key,
+                      int64_t key_first, int64_t span, int32_t n_bands, const double* spheres, const double* opl,
+                      const double* moments, double* rec, void* stream);
+int ot_psf_field_sum(int64_t n, const double* rec, int32_t n_fields, int32_t n_bands, const int64_t* starts, const double* radius,
+                     int32_t n_px, double size, int32_t n_planes, const double* dz, int64_t* table, double* workspace, double* field,
+                     double* sums, void* stream);
+int ot_psf_field_combine(int32_t n_fields, int32_t n_bands, int32_t n_planes, int32_t n_px, const double* field, const double* sums,
+                         double* intensity, double* band_strehl, double* strehl, double* g, double* noise_floor, void* stream);
+int ot_psf_field_otf(int32_t n_fields, int32_t n_planes, int32_t n_px, double size, const double* intensity,
+                     const double* noise_floor, const double* t, int32_t n_freq, const double* frequencies, double* out, void* stream);
+
 /* ---- field-dependent convolution (ot.convolve_field; no counterpart in optrace) -----------------------------------
  * An image spread by a gy x gx grid of point spread functions, one per field point, blended bilinearly over the image's
  * interior: the PSF belongs to the SOURCE pixel.  Planar layouts: img[n_ch][ny][nx], psf[gy][gx][py][px],

@@ -26,6 +26,7 @@ from .field import FieldAnalysis
 from .mtf import MTFAnalysis
 from .spot_diagram import SpotDiagram
 from .wavefront_field import WavefrontField
+from .psf_field import HuygensField
 from .fans import RayFans
 from .ray_storage import RayStorage
 from .raytracer import Raytracer

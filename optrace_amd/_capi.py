@@ -232,6 +232,12 @@ SIGNATURES = {
     "ot_psf_stack_workspace": (i64, [i64, i32, i32, i32]),
     "ot_psf_stack": (C.c_int, [i64, vp, i32, C.POINTER(i64), C.c_double, i32, C.c_double, i32, C.POINTER(C.c_double), vp, vp, vp, vp]),
     "ot_psf_combine": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ot_psf_field_workspace": (i64, [i64, i32, i32, i32, i32]),
+    "ot_psf_field_rays": (C.c_int, [C.POINTER(Rays), C.POINTER(i64), i32, i32, vp, i64, i64, i32, vp, vp, vp, vp, vp]),
+    "ot_psf_field_sum": (C.c_int, [i64, vp, i32, i32, C.POINTER(i64), C.POINTER(C.c_double), i32, C.c_double, i32,
+                                   C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
+    "ot_psf_field_combine": (C.c_int, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ot_psf_field_otf": (C.c_int, [i32, i32, i32, C.c_double, vp, vp, C.POINTER(C.c_double), i32, C.POINTER(C.c_double), vp, vp]),
     "ot_convolve_field": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]),
     "ot_sample_stratified": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(SourceRange), i32, u64, i64, vp, vp, vp]),
     "ot_sample_positions": (C.c_int, [C.POINTER(Source), C.POINTER(SourceRange), i32, u64, i64, vp, vp]),
@@ -262,6 +268,7 @@ SD_MAX_PX, SD_MAX_CELLS, SD_BLOCKS, SD_MIN_BLOCKS, SD_LDS_BYTES = 1024, 1 << 28,
 FAN_M, FAN_BIN_M, FAN_MAX_BINS = 13, 6, 256  # OT_FAN_*
 PSF_MAX_PX, PSF_REC = 1024, 6  # OT_PSF_*
 PSF_MAX_BANDS, PSF_MAX_PLANES, PSF_STACK_CAP = 32, 64, 1 << 28  # OT_PSF_MAX_BANDS, OT_PSF_MAX_PLANES, OT_PSF_STACK_CAP (doubles)
+PSFF_MAX_FREQ, PSFF_MAX_CHUNKS = 64, 65535  # OT_PSFF_MAX_FREQ; OT_PSFF_MAX_CHUNKS of csrc/ot_psf_field_api.hip
 CONVF_MAX_PSF, CONVF_MAX_GRID = 512, 64  # OT_CONVF_MAX_PSF, OT_CONVF_MAX_GRID
 
 
@@ -289,6 +296,28 @@ def psf_stack_ws(n: int, n_bands: int, n_px: int, n_planes: int) -> int:
     tiles = -(-points // 1024)
     chunks = max(1, min(1024 * min(n_planes, 4) // (tiles * n_planes), -(-n // 128)))
     return n_planes * (chunks + n_bands - 1) * (2 * points + 2)
+
+
+def psf_field_chunks(n: int, n_fields: int, n_bands: int, n_px: int, n_planes: int) -> int:
+    """Chunks of records that ot_psf_field_sum takes at the most, a bound that needs no starts.  Every field with a record is aimed
+    at the workgroups of a stack of its own: with g such fields the chunks are those of `psf_stack_ws` for a field of mean size,
+    ceil(n / g) records, times g -- the largest over g <= n_fields --; no chunk straddles a cell, which costs n_fields * n_bands - 1
+    chunks at the most.  Above PSFF_MAX_CHUNKS the call is refused."""
+    tiles = -(-(n_px * n_px + 1) // 1024)
+    aimed = 1024 * min(n_planes, 4) // (tiles * n_planes)
+    most = max(g * max(1, min(aimed, -(-(-(-n // g)) // 128))) for g in range(1, n_fields + 1))
+    return most + n_fields * n_bands - 1
+
+
+def psf_field_ws(n: int, n_fields: int, n_bands: int, n_px: int, n_planes: int) -> int:
+    """ot_psf_field_workspace(n, n_fields, n_bands, n_px, n_planes): doubles of workspace for ot_psf_field_sum: per plane and chunk
+    of `psf_field_chunks` Re and Im of every point, sum a and sum a^2.  With one field it is psf_stack_ws."""
+    return n_planes * psf_field_chunks(n, n_fields, n_bands, n_px, n_planes) * (2 * (n_px * n_px + 1) + 2)
+
+
+def psf_field_table(cells: int) -> int:
+    """OT_PSF_FIELD_TABLE(cells): 8-byte words of the cell table that ot_psf_field_sum keeps on the device."""
+    return 4 * cells + 2
 
 
 _lib = None

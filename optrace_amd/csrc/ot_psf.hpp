@@ -9,7 +9,8 @@
 // OT_PSF_PPL per lane, and walks one chunk of the rays, whose records are the same for every lane and arrive by scalar loads.
 // Partial sums per (plane, chunk, point) go to the workspace; a last kernel adds the chunks of a band in index order.  Tiles and
 // chunks follow from (n, n_px, the starts and the number of planes) alone: two calls return the same bits.
-// Defines kernels that are no templates: included by ot_psf_api.hip alone.
+// Defines kernels that are no templates: included by ot_psf_api.hip alone -- and, with OT_PSF_NO_KERNELS defined, for the lanes'
+// arithmetic and the chunk rule without the kernels, by ot_psf_field_api.hip.
 #pragma once
 #include "ot_device.hpp"
 #include "ot_wavefront_ray.hpp"
@@ -40,6 +41,7 @@ static inline PsfShape psf_shape(int64_t n, int n_px) {
     return s;
 }
 
+#ifndef OT_PSF_NO_KERNELS
 // One thread per ray of [first, first + count): the sphere step of wf_paths_kernel on p, w and n of the storage, the wavelength,
 // the path that ot_wavefront_paths left in `opl` and its mean from the moments record.  rec[6][count].
 __global__ __launch_bounds__(OT_PSF_THREADS) void psf_rays_kernel(ot_rays R, int64_t first, int64_t count, int k, double cx, double cy,
@@ -69,6 +71,8 @@ __global__ __launch_bounds__(OT_PSF_THREADS) void psf_rays_kernel(ot_rays R, int
     rec[i + count * PSF_KAPPA] = kappa;
     rec[i + count * PSF_A] = a;
 }
+
+#endif  // OT_PSF_NO_KERNELS
 
 // a ray's record in scalar registers (the index is the same in every lane: the constant address space makes these scalar loads)
 struct PsfRec {
@@ -163,6 +167,7 @@ static inline PsfShape psf_stack_shape(int64_t n, int n_px, int n_planes) {
     return s;
 }
 
+#ifndef OT_PSF_NO_KERNELS
 // The hot kernel.  Workgroup (tile, chunk, plane): wave wv, lane l holds the points tile * OT_PSF_TILE + (wv * OT_PSF_PPL + j) * 64 + l,
 // j < OT_PSF_PPL, of the plane's dz; a wave whose points all lie beyond the last one leaves at once.  The chunk finds its band and
 // its ray range from the starts; a chunk behind its band's last ray stores zeros.  part[planes][chunks][2 P + 2].
@@ -291,3 +296,4 @@ __global__ __launch_bounds__(OT_PSF_THREADS) void psf_combine_kernel(int K, int 
         if (z == 0) noise_floor[0] = floor_;
     }
 }
+#endif  // OT_PSF_NO_KERNELS

@@ -49,6 +49,8 @@ from . import spot_diagram as _spot_diagram
 from .spot_diagram import SpotDiagram
 from . import wavefront_field as _wavefront_field
 from .wavefront_field import WavefrontField
+from . import psf_field as _psf_field
+from .psf_field import HuygensField
 from . import fans as _fans
 from .fans import RayFans
 from .geometry.ray_source import RaySource
@@ -1018,6 +1020,33 @@ class Raytracer(Group):
         return _wavefront_field.analyse(self.rays, ranges, k, table.origin(k, None), bands, n_zernike, sphere, focus, radius,
                                         pupil_radius, reference, reference_field, sources, field,
                                         long_desc=f"Wavefront of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
+
+    def huygens_field(self, sources=None, section: int = None, bands="lines", n_px: int = 64, size: float = None, dz=0.0,
+                      focus=None, radius=None, frequencies=None, reference: float = None,
+                      reference_field: int = 0) -> HuygensField:
+        """Huygens PSF and diffraction MTF across the field, no counterpart in optrace: every chosen ray source is a field point, and
+        per field point the polychromatic through-focus diffraction image of `huygens_stack` about a reference sphere of the
+        field's own is summed on the GPU in one call for all fields, bands and planes, with its transfer function along the
+        field's tangential direction and across it (psf_field.py).  sources, section, bands, reference, reference_field: as for
+        `field_analysis`; n_px, dz: as for `huygens_stack`, the planes of a field lie at its focus z + dz; size: the side of every
+        tile in mm, default the largest over the fields of ten mean wavelengths over the pupil radius; focus (F, 3), radius (F,)
+        or one number: centre and signed radius of the sphere per field, default that of `wavefront_field(sphere="field")`, the
+        sphere of the field's reference band for all its bands -- axial colour shows as each band's defocus, lateral colour as
+        its offset inside the tile --, and a collimated field has none (its rays are counted in `n_no_sphere`); frequencies: 1
+        to 64 values of 0 or above in cycles per mm, none above the sampling limit n_px / (2 size), default 17 equal steps from 0
+        to that limit.  `HuygensField.grid()` is what `ot.convolve_field` takes."""
+        table = SectionTable(self)
+        sources, bands, _, reference = _field.check_arguments(table.nt, len(self.ray_sources), sources, section, bands, None, reference,
+                                                              reference_field, None)
+        size, dz, focus, radius, frequencies = _psf_field.check_arguments(table.nt, len(sources), section, n_px, size, dz, focus, radius,
+                                                                          frequencies)
+        ranges, k, axis, positions, tangents, field, power = self._field_points(table, sources, section)
+        if table.ideal_before(k):
+            warning(f"An ideal lens lies before section {k}: the optical path through an ideal lens is not defined, "
+                    f"the wavefront figures hold up to what it would add.")
+        return _psf_field.analyse(self.rays, ranges, k, table.origin(k, None), bands, n_px, size, dz, focus, radius, frequencies,
+                                  reference, reference_field, sources, field,
+                                  long_desc=f"Huygens PSF of {', '.join(self._rays_tag(s) for s in sources)} behind section {k}")
 
     def ray_fans(self, source_index: int = 0, section: int = None, bands="lines", focus=None, radius: float = None,
                  n_bins: int = 32, slab: float = 0.1, pupil_radius: float = None) -> RayFans:
